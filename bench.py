@@ -10,6 +10,10 @@ train mode (every dropout site on, incl. the one inside the pair classifiers), b
 N > 1 the RCCL all-reduce of all 127 M gradients (one flat bf16 buffer in stage order, ~64 MB chunks).  No optimizer step (the
 metric is fwd+bwd): the bf16 working copies of the fp32 master weights are therefore built once and reused; what
 refreshing them after an optimizer step costs is reported beside the metric (`with_weight_recast`).  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times `--steps` steps and prints the line (`value`, `ms_per_step`, ...).  `--full` adds every side
+measurement: the per-kernel roofline figures, ragged batches, weight re-cast, eval forward, bf16-vs-fp32 index agreement, the
+optimizer step and the CPU baseline.  `--dump-outputs DIR` writes what the last timed step returned (see dump_outputs()).
 """
 from __future__ import annotations
 
@@ -109,6 +113,41 @@ def cpu_baseline(pcfg, seq_len, n_lines, seed):
                       f"best of 2 after 1 warm-up ({dr:.2f}s)"}
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+GRAD_SAMPLE_MAX = 32768             # gradient elements kept per parameter tensor (a fixed, seeded sample of the larger ones)
+
+
+def dump_outputs(dirname: str, outputs, named_params, budget_bytes: int = DUMP_BUDGET_BYTES) -> int:
+    """Write what a caller of the timed step receives as DIR/<name>.npy: every tensor field of the model output (loss, the
+    five head losses, ...) and every parameter gradient, as float32 (float64 for float64 / integer tensors).  Gradients larger
+    than the per-tensor share of the budget are sampled at sorted indices drawn from a generator seeded by the parameter's
+    name, so two runs (or two builds) with the same arguments write the same positions.  Returns the bytes written."""
+    import zlib
+    import numpy as np
+
+    def host(t):
+        t = t.detach()
+        return (t.double() if t.dtype == torch.float64 or not t.is_floating_point() else t.float()).cpu().numpy()
+
+    arrays = {k: host(v) for k, v in outputs.items() if torch.is_tensor(v)}
+    grads = [(n, p.grad) for n, p in named_params if p.grad is not None]
+    left = budget_bytes - sum(a.nbytes for a in arrays.values())
+    per = max(1, min(GRAD_SAMPLE_MAX, left // (4 * max(1, len(grads)))))
+    for n, g in grads:
+        g = g.detach().reshape(-1)
+        if g.numel() > per:
+            gen = torch.Generator().manual_seed(zlib.crc32(n.encode()))
+            idx = torch.randint(g.numel(), (per,), generator=gen).sort().values
+            g = g[idx.to(g.device)]
+        arrays["grad." + n] = host(g)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= budget_bytes, (total, budget_bytes)
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
+    return total
+
+
 def plan_launch(gpus: int, environ) -> tuple:
     """How `bench.py --gpus N` becomes N ranks (reference: `torchrun --nproc_per_node N start/run_rfund.py`, README.md:206-218).
     ("run",)          this process IS a rank (N = 1, or torch.distributed.run / torchrun started it: WORLD_SIZE == N);
@@ -161,7 +200,13 @@ def main():
                          "or 0 with --no-cpu-baseline, i.e. in the quick runs of tools/)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--eval-forward", action="store_true", help="time eval forward only (reported as a side metric)")
+    ap.add_argument("--full", action="store_true", help="also run every side measurement (roofline, ragged, weight re-cast, "
+                    "eval forward, index agreement, optimizer step, CPU baseline); without it only the timed steps run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (losses, sampled parameter gradients) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.trained_agree_steps < 0:
         args.trained_agree_steps = 0 if args.no_cpu_baseline else 2000
 
@@ -210,11 +255,13 @@ def main():
 
     batches = [make_batch(s) for s in range(4)]     # inputs resident in HBM before the timed region
 
-    def step(i):
+    def step(i, keep=None):
         for p in model.parameters():
             p.grad = None
         out = net(**batches[i % len(batches)])
         out["loss"].backward()
+        if keep is not None:              # --dump-outputs: the last timed step's output fields (detached, no copy)
+            keep.update((k, v.detach()) for k, v in out.items() if torch.is_tensor(v))
         return out["loss"].detach()       # (what a training loop logs; holding the loss itself would keep the step's graph alive through the next step)
 
     for i in range(args.warmup):
@@ -222,14 +269,15 @@ def main():
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
-    ops.TIMER.reset(True)
+    last_out = {} if args.dump_outputs and rank == 0 else None
+    ops.TIMER.reset(args.full)        # per-launch events of the roofline kernels: --full only
     torch.cuda.synchronize()
     dbg_alloc = os.environ.get("PENEO_BENCH_ALLOC_STATS") == "1"       # tools/: device allocations and host time per step inside the timed region
     if dbg_alloc:
         ms0 = torch.cuda.memory_stats(dev); host_t = []
     t0 = time.perf_counter()
     for i in range(args.steps):
-        loss = step(i)
+        loss = step(i, last_out if i == args.steps - 1 else None)
         if dbg_alloc:
             host_t.append(time.perf_counter())
     torch.cuda.synchronize()
@@ -250,11 +298,14 @@ def main():
     eb = ops.TIMER.durations_ms("embed_bwd")          # word / position / box table scatter (fp32 atomics)
     ops.TIMER.reset(False)
     loss_val = float(loss.detach())
+    if last_out is not None:          # before any side measurement overwrites the gradients
+        dump_outputs(args.dump_outputs, last_out, model.named_parameters())
+        del last_out
 
     # side line: ragged documents (300..510 tokens), batch cut to its longest document rounded up to a multiple
     # of 8 like the reference's collator (data/collator.py:110-116): N varies from batch to batch (masked tails everywhere)
     ragged = None
-    if not args.no_ragged and world == 1:
+    if args.full and not args.no_ragged and world == 1:
         rb = []
         for s_ in range(4):
             b_ = synthetic_rfund_batch(B, args.seq_len, args.lines, vocab, seed=7000 + s_, ragged=True, pad_to_longest=True)
@@ -280,69 +331,70 @@ def main():
                   "padded_lengths": [int(b_["input_ids"].shape[1]) for b_ in rb],
                   "mean_tokens": round(float(sum(float(b_["attention_mask"].sum()) for b_ in rb) / (4 * B)), 1)}
 
-    # side metric: the same step when the parameters have changed since the last forward (i.e. behind an optimizer step): every
-    # working-precision weight copy is re-cast / re-packed first (engine.WeightCache); not part of `value` (no optimizer step)
-    from peneo_amd.model.engine import bump_param_epoch
-    nrc = max(4, args.steps // 2)
-    for i in range(2):
-        bump_param_epoch(); step(i)
-    torch.cuda.synchronize()
-    trc = time.perf_counter()
-    for i in range(nrc):
-        bump_param_epoch(); step(i)
-    torch.cuda.synchronize()
-    recast_ms = (time.perf_counter() - trc) * 1e3 / nrc
-
-    # side metric: eval forward only (the "encoder + pair-head forward" roofline target of BASELINE.md §5)
-    model.eval()
-    with torch.no_grad():
+    if args.full:
+        # side metric: the same step when the parameters have changed since the last forward (i.e. behind an optimizer step): every
+        # working-precision weight copy is re-cast / re-packed first (engine.WeightCache); not part of `value` (no optimizer step)
+        from peneo_amd.model.engine import bump_param_epoch
+        nrc = max(4, args.steps // 2)
         for i in range(2):
-            net_out = model(**batches[i])
+            bump_param_epoch(); step(i)
         torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        nf = max(3, args.steps // 2)
-        for i in range(nf):
-            model(**batches[i % len(batches)])
+        trc = time.perf_counter()
+        for i in range(nrc):
+            bump_param_epoch(); step(i)
         torch.cuda.synchronize()
-        fwd_ms = (time.perf_counter() - t1) * 1e3 / nf
+        recast_ms = (time.perf_counter() - trc) * 1e3 / nrc
 
-    # side metric (north_star: "BIO/link indices bit-exact"): how many of the 5 x B x 130 816 pair-tag indices (argmax over the
-    # classes, model/peneo_decoder.py:98-114) the bf16 path BENCHMARKED here decides differently from the fp32 parity path of
-    # the same weights on the same batch; `clear` counts only pairs whose fp32 margin (top1 - top2 logit) exceeds 0.05
-    indices_agree = None
-    if world == 1:
+        # side metric: eval forward only (the "encoder + pair-head forward" roofline target of BASELINE.md §5)
+        model.eval()
         with torch.no_grad():
-            o16 = model(**batches[0])
-            model.set_compute_dtype(torch.float32)
-            o32 = model(**batches[0])
-            model.set_compute_dtype(dtype)
-            maps, flips, clear, total = {}, 0, 0, 0
-            for k in o32:
-                if not k.endswith("_shaking_outputs"):
-                    continue
-                a16, a32 = o16[k].argmax(-1), o32[k].argmax(-1)
-                diff = a16 != a32
-                top2 = o32[k].float().topk(2, dim=-1).values
-                dc = diff & ((top2[..., 0] - top2[..., 1]) > 0.05)
-                maps[k[:-len("_shaking_outputs")]] = {"flips": int(diff.sum()), "clear_flips": int(dc.sum()), "of": diff.numel()}
-                flips += int(diff.sum()); clear += int(dc.sum()); total += diff.numel()
-            indices_agree = {"bf16_vs_fp32_flips": flips, "clear_flips": clear, "of": total,
-                             "flip_rate": round(flips / max(1, total), 9), "maps": maps}
-            del o16, o32
+            for i in range(2):
+                net_out = model(**batches[i])
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            nf = max(3, args.steps // 2)
+            for i in range(nf):
+                model(**batches[i % len(batches)])
+            torch.cuda.synchronize()
+            fwd_ms = (time.perf_counter() - t1) * 1e3 / nf
 
-    # side metric: the optimizer step that completes a training iteration (fused multi-tensor AdamW, reference groups);
-    # not part of `value` (the metric is fwd + bwd)
-    from peneo_amd.optim import FusedAdamW, peneo_param_groups
-    model.train()
-    step(0)
-    opt = FusedAdamW(peneo_param_groups(model, 5e-5, 0.01, 30.0), max_grad_norm=1.0)   # HF Trainer's default clipping, fused
-    opt.step()
-    torch.cuda.synchronize()
-    t2 = time.perf_counter()
-    for _ in range(3):
+        # side metric (north_star: "BIO/link indices bit-exact"): how many of the 5 x B x 130 816 pair-tag indices (argmax over the
+        # classes, model/peneo_decoder.py:98-114) the bf16 path BENCHMARKED here decides differently from the fp32 parity path of
+        # the same weights on the same batch; `clear` counts only pairs whose fp32 margin (top1 - top2 logit) exceeds 0.05
+        indices_agree = None
+        if world == 1:
+            with torch.no_grad():
+                o16 = model(**batches[0])
+                model.set_compute_dtype(torch.float32)
+                o32 = model(**batches[0])
+                model.set_compute_dtype(dtype)
+                maps, flips, clear, total = {}, 0, 0, 0
+                for k in o32:
+                    if not k.endswith("_shaking_outputs"):
+                        continue
+                    a16, a32 = o16[k].argmax(-1), o32[k].argmax(-1)
+                    diff = a16 != a32
+                    top2 = o32[k].float().topk(2, dim=-1).values
+                    dc = diff & ((top2[..., 0] - top2[..., 1]) > 0.05)
+                    maps[k[:-len("_shaking_outputs")]] = {"flips": int(diff.sum()), "clear_flips": int(dc.sum()), "of": diff.numel()}
+                    flips += int(diff.sum()); clear += int(dc.sum()); total += diff.numel()
+                indices_agree = {"bf16_vs_fp32_flips": flips, "clear_flips": clear, "of": total,
+                                 "flip_rate": round(flips / max(1, total), 9), "maps": maps}
+                del o16, o32
+
+        # side metric: the optimizer step that completes a training iteration (fused multi-tensor AdamW, reference groups);
+        # not part of `value` (the metric is fwd + bwd)
+        from peneo_amd.optim import FusedAdamW, peneo_param_groups
+        model.train()
+        step(0)
+        opt = FusedAdamW(peneo_param_groups(model, 5e-5, 0.01, 30.0), max_grad_norm=1.0)   # HF Trainer's default clipping, fused
         opt.step()
-    torch.cuda.synchronize()
-    opt_ms = (time.perf_counter() - t2) * 1e3 / 3
+        torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        for _ in range(3):
+            opt.step()
+        torch.cuda.synchronize()
+        opt_ms = (time.perf_counter() - t2) * 1e3 / 3
 
     # side metric: `indices_agree` above is taken on random-init weights, where every logit sits in a near-tie
     # band.  What the reference decodes in practice (model/peneo_decoder.py:98-114) are separated logits: train this model on ONE
@@ -350,7 +402,7 @@ def main():
     # pair-tag indices the bf16 path decides differently from the fp32 path of the same trained weights, and compare the decoded
     # spot lists (get_spots_from_shaking_tag) of the two precisions.  Outside the timed region; not part of `value`.
     indices_agree_trained = None
-    if world == 1 and args.trained_agree_steps > 0 and args.backbone == "layoutlmv3":
+    if args.full and world == 1 and args.trained_agree_steps > 0 and args.backbone == "layoutlmv3":
         from peneo_amd.model.peneo_decoder import HandshakingTaggingScheme
         # (eval mode: no dropout - the run is the same every time up to the order of fp32 atomics, and the positives separate in
         # fewer steps; the gradient path is the one the parity tests use)
@@ -488,26 +540,28 @@ def main():
                        "docs_per_gpu": B, "seq_len": args.seq_len, "lines": args.lines,
                        "parallelism": f"dp{world}", "final_loss": round(loss_val, 5)},
             "input_checks": True,               # bbox range check on in the timed region (device flag, read after it)
-            "roofline": dom_roof,
-            "roofline_pair_heads_fwd": fwd_roof,
-            "forward_only": {"ms_per_batch": round(fwd_ms, 3), "docs_per_s": round(B * 1e3 / fwd_ms, 1),
-                             "tflops_algorithmic": round(FWD_GFLOP_PER_DOC * B / fwd_ms, 1),
-                             "frac_of_mfma_peak": round(FWD_GFLOP_PER_DOC * B / fwd_ms / PEAK_BF16_TFLOPS, 4)},
-            "indices_agree": indices_agree,
-            "indices_agree_trained": indices_agree_trained,
-            "ragged": ragged,
-            "embed_bwd": ({"avg_launch_ms": round(sum(eb) / len(eb), 4), "launches": len(eb), "vocab": vocab,
-                           # algorithmic bytes: every token reads its d_x row (H * 2 B) and adds H fp32 values into 6 tables
-                           "GBps_algorithmic": round(B * args.seq_len * pcfg["backbone_config"]["hidden_size"] * (2 + 2 * 4 * 2)
-                                                     / (sum(eb) / len(eb) * 1e-3) / 1e9, 1), "peak_GBps": 8000.0} if eb else None),
-            "with_weight_recast": {"ms_per_step": round(recast_ms, 3), "docs_per_s": round(world * B * 1e3 / recast_ms, 1)},
-            "optimizer_step_ms": round(opt_ms, 3),
-            "train_tflops_algorithmic": round(3 * FWD_GFLOP_PER_DOC * docs / elapsed / 1e3, 1),
         }
-        if not args.no_cpu_baseline and world == 1 and args.size == "base" and args.backbone == "layoutlmv3":
-            res["cpu_baseline"] = cpu_baseline(pcfg, args.seq_len, args.lines, seed=7)
-        else:
-            res["cpu_baseline"] = None
+        if args.full:
+            res.update({
+                "roofline": dom_roof,
+                "roofline_pair_heads_fwd": fwd_roof,
+                "forward_only": {"ms_per_batch": round(fwd_ms, 3), "docs_per_s": round(B * 1e3 / fwd_ms, 1),
+                                 "tflops_algorithmic": round(FWD_GFLOP_PER_DOC * B / fwd_ms, 1),
+                                 "frac_of_mfma_peak": round(FWD_GFLOP_PER_DOC * B / fwd_ms / PEAK_BF16_TFLOPS, 4)},
+                "indices_agree": indices_agree,
+                "indices_agree_trained": indices_agree_trained,
+                "ragged": ragged,
+                "embed_bwd": ({"avg_launch_ms": round(sum(eb) / len(eb), 4), "launches": len(eb), "vocab": vocab,
+                               # algorithmic bytes: every token reads its d_x row (H * 2 B) and adds H fp32 values into 6 tables
+                               "GBps_algorithmic": round(B * args.seq_len * pcfg["backbone_config"]["hidden_size"] * (2 + 2 * 4 * 2)
+                                                         / (sum(eb) / len(eb) * 1e-3) / 1e9, 1), "peak_GBps": 8000.0} if eb else None),
+                "with_weight_recast": {"ms_per_step": round(recast_ms, 3), "docs_per_s": round(world * B * 1e3 / recast_ms, 1)},
+                "optimizer_step_ms": round(opt_ms, 3),
+            })
+        res["train_tflops_algorithmic"] = round(3 * FWD_GFLOP_PER_DOC * docs / elapsed / 1e3, 1)
+        if args.full:
+            cpu = not args.no_cpu_baseline and world == 1 and args.size == "base" and args.backbone == "layoutlmv3"
+            res["cpu_baseline"] = cpu_baseline(pcfg, args.seq_len, args.lines, seed=7) if cpu else None
         print(json.dumps(res))
     if world > 1:
         dist.destroy_process_group()

@@ -808,6 +808,49 @@ def test_bench_starts_its_own_ranks(tmp_path):
     assert r2.returncode != 0 and not [l for l in r2.stdout.splitlines() if l.startswith("{")]
 
 
+def test_bench_plain_run_is_lean_dumps_its_outputs_and_full_adds_the_side_measurements(tmp_path):
+    """`bench.py` without --full times exactly --steps steps and prints the headline line only; --dump-outputs writes the last
+    timed step's losses and sampled gradients (same inputs on every run: two runs agree up to summation order); --full brings
+    back every side measurement."""
+    import json, os, subprocess, sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+    def run(*extra):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--docs-per-gpu", "2", *extra],
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        return json.loads(lines[0])
+
+    side = ("roofline", "roofline_pair_heads_fwd", "forward_only", "indices_agree", "indices_agree_trained", "ragged",
+            "embed_bwd", "with_weight_recast", "optimizer_step_ms", "cpu_baseline")
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"out{k}"
+        rec = run("--steps", "3", "--warmup", "1", "--dump-outputs", str(d))
+        assert rec["steps"] == 3 and rec["ms_per_step"] > 0 and rec["value"] > 0 and rec["unit"] == "docs/s", rec
+        assert rec["higher_is_better"] is True and rec["dtype"] == "bf16" and not any(s in rec for s in side), rec
+        files = sorted(os.listdir(d))
+        assert "loss.npy" in files and sum(f.startswith("grad.") for f in files) > 100, files
+        arrs = {f: np.load(d / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+        assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        assert abs(float(arrs["loss.npy"]) - rec["config"]["final_loss"]) < 1e-4
+        dumps.append(arrs)
+    a, b = dumps
+    assert sorted(a) == sorted(b) and all(a[f].shape == b[f].shape for f in a)
+    assert abs(float(a["loss.npy"]) - float(b["loss.npy"])) < 1e-3 * max(1.0, abs(float(b["loss.npy"])))
+    ga = np.concatenate([a[f].ravel() for f in sorted(a) if f.startswith("grad.")]).astype(np.float64)
+    gb = np.concatenate([b[f].ravel() for f in sorted(b) if f.startswith("grad.")]).astype(np.float64)
+    assert np.linalg.norm(ga - gb) <= 2e-2 * np.linalg.norm(gb)
+
+    rec = run("--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline")
+    assert all(s in rec for s in side), sorted(rec)
+    assert rec["forward_only"]["ms_per_batch"] > 0 and rec["ragged"]["ms_per_step"] > 0 and rec["roofline"]["launches"] >= 2
+
+
 def test_fused_adamw_resumes_from_state_dict_and_from_torch_adamw():
     """state_dict() carries torch.optim.AdamW's layout (per-parameter `step`, exp_avg, exp_avg_sq): 3 steps + save + load
     into a fresh optimizer + 3 steps == 6 uninterrupted steps of torch.optim.AdamW; a torch AdamW checkpoint (the

@@ -272,6 +272,42 @@ def test_bench_launch_plan_never_relabels_a_smaller_job():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4"], env=dict(os.environ, WORLD_SIZE="1", RANK="0"),
                        capture_output=True, text=True, timeout=300)
     assert r.returncode == 2 and "WORLD_SIZE=1" in r.stderr, (r.returncode, r.stderr[-400:])
+    # --steps sets the number of timed steps: none is not a measurement
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 2 and "--steps" in r.stderr, (r.returncode, r.stderr[-400:])
+
+
+def test_bench_dump_outputs_writes_a_fixed_sample_within_budget(tmp_path):
+    """bench.dump_outputs (--dump-outputs DIR): every tensor output field and every parameter gradient as DIR/<name>.npy in
+    float32 / float64; gradients above the per-tensor share are sampled at positions fixed by the parameter's name, so two
+    dumps of the same step hold the same elements, and the whole dump stays within its byte budget."""
+    import sys
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    torch.manual_seed(0)
+    params = {"big.weight": torch.nn.Parameter(torch.randn(300, 200)), "small.bias": torch.nn.Parameter(torch.randn(7)),
+              "frozen.weight": torch.nn.Parameter(torch.randn(3))}
+    params["big.weight"].grad = torch.randn(300, 200)
+    params["small.bias"].grad = torch.randn(7)
+    outputs = {"loss": torch.tensor(1.25, dtype=torch.bfloat16), "orig_bbox": torch.arange(8).reshape(2, 4), "note": "not a tensor"}
+    budget = 64 * 1024
+    n1 = bench.dump_outputs(str(tmp_path / "a"), outputs, params.items(), budget_bytes=budget)
+    n2 = bench.dump_outputs(str(tmp_path / "b"), outputs, params.items(), budget_bytes=budget)
+    assert n1 == n2 <= budget
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["grad.big.weight.npy", "grad.small.bias.npy", "loss.npy", "orig_bbox.npy"], names
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), n
+        total += a.nbytes
+    assert total == n1
+    assert float(np.load(tmp_path / "a" / "loss.npy")) == 1.25
+    assert np.array_equal(np.load(tmp_path / "a" / "orig_bbox.npy"), np.arange(8).reshape(2, 4))
+    assert np.array_equal(np.load(tmp_path / "a" / "grad.small.bias.npy"), params["small.bias"].grad.numpy())
+    big = np.load(tmp_path / "a" / "grad.big.weight.npy")
+    assert 0 < big.size < 300 * 200 and np.isin(big, params["big.weight"].grad.numpy().reshape(-1)).all()
 
 
 def test_step_sized_buffers_are_kept_and_handed_out_once():

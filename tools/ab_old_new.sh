@@ -4,6 +4,6 @@
 R=${1:-3}; shift
 for i in $(seq $R); do
   for d in . _old; do
-    ( cd $d && python bench.py --no-cpu-baseline --no-ragged --steps 20 "$@" 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$d', d['value'], d['ms_per_step'], d['forward_only']['ms_per_batch'])" )
+    ( cd $d && python bench.py $(grep -q -- --full bench.py && echo --full) --no-cpu-baseline --no-ragged --steps 20 "$@" 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$d', d['value'], d['ms_per_step'], d['forward_only']['ms_per_batch'])" )
   done
 done

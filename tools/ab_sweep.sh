@@ -15,7 +15,7 @@ for round in $(seq ${ROUNDS:-2}); do
   for v in "${VALS[@]}"; do
     echo -n "$VAR=$v  "
     if [ $# -gt 0 ]; then env $VAR=$v "$@" 2>&1 | grep -v amdgpu.ids | tail -${TAIL:-1}
-    else env $VAR=$v python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-ragged 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['forward_only']['ms_per_batch'])"
+    else env $VAR=$v python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-ragged 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['forward_only']['ms_per_batch'])"
     fi
   done
 done

@@ -7,7 +7,7 @@ rocprofv3 --list-avail 2>/dev/null | grep -io "SQC_ICACHE[A-Z_]*\|SQ_IFETCH[A-Z_
 cat $OUT/avail.txt | tr '\n' ' '; echo
 for C in "SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQ_WAVE_CYCLES" "SQ_IFETCH SQ_WAIT_INST_ANY SQ_WAVE_CYCLES SQ_BUSY_CYCLES"; do
   rm -rf $OUT/tmp
-  rocprofv3 --pmc $C -d $OUT/tmp -o p -f csv -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-ragged --trained-agree-steps 0 "$@" > /dev/null 2>&1
+  rocprofv3 --pmc $C -d $OUT/tmp -o p -f csv -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-ragged --trained-agree-steps 0 "$@" > /dev/null 2>&1
   python3 - <<'PY'
 import csv, glob, collections
 fs = glob.glob("gpurun_out/icache/tmp/**/*counter_collection.csv", recursive=True)

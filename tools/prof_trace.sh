@@ -1,7 +1,8 @@
-# kernel trace (csv) of a short bench run -> gpurun_out/$1 ; run through gpurun:  bash tools/prof_trace.sh NAME [bench args]
+# kernel trace (csv) of a short bench run (--full) -> $PROF_OUT/NAME (default prof_out/):  bash tools/prof_trace.sh NAME [bench args]
 NAME=${1:-trace}; shift
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
+OUT=${PROF_OUT:-prof_out}; mkdir -p $OUT
 python bench.py --steps 2 --warmup 1 --no-cpu-baseline > /dev/null 2>&1
-rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/$NAME -o run -- python3 bench.py --steps 4 --warmup 2 --no-cpu-baseline "$@" > gpurun_out/$NAME.log 2>&1
-find gpurun_out/$NAME -name "*kernel_trace.csv" | head -1 | xargs -I{} python tools/timeline.py {} 2 > gpurun_out/$NAME.timeline.txt 2>&1
-head -50 gpurun_out/$NAME.timeline.txt
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$NAME -o run -- python3 bench.py --full --steps 4 --warmup 2 --no-cpu-baseline "$@" > $OUT/$NAME.log 2>&1
+find $OUT/$NAME -name "*kernel_trace.csv" | head -1 | xargs -I{} python tools/timeline.py {} 2 > $OUT/$NAME.timeline.txt 2>&1
+head -50 $OUT/$NAME.timeline.txt
