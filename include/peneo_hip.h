@@ -86,6 +86,12 @@ typedef struct peneo_gemm_epilogue {
   float* a_colsum;
 } peneo_gemm_epilogue;
 
+/* Workspace: peneo_gemm_workspace_bytes(M, N, K, split_k) bytes, 16-byte aligned, used by one call at a time (the next call on the
+ * same stream may reuse it).  It holds the fp32 partials of a split reduction, and the flags and fp32 slabs of a persistent launch
+ * whose ranges cut tiles (stream-k; large bf16 problems with k-major A and B, few tiles and a deep K), so it may be non-zero with
+ * split_k == 1.  Its size follows peneo_gemm_set_sk_mode.  A stream-k launch zeroes its flags on `stream` before it starts, so a
+ * call captured into a graph runs the same kernels as an eager one and replays with the workspace it was captured with.  A call
+ * that needs the workspace and gets a null, smaller or misaligned one returns PENEO_ERR_INVALID. */
 size_t peneo_gemm_workspace_bytes(int M, int N, int K, int split_k);
 int peneo_gemm(int dtype, int a_kmajor, int b_kmajor, int M, int N, int K,
                const void* A, int64_t lda, const void* B, int64_t ldb,
@@ -545,7 +551,8 @@ typedef struct peneo_encoder_layer_grads {
 } peneo_encoder_layer_grads;
 /* sizeof of the structs shared with a binding: 0 peneo_gemm_epilogue, 1 peneo_encoder_layer, 2 peneo_encoder_layer_grads */
 size_t peneo_struct_bytes(int which);
-/* split-k workspace of the layer's GEMMs: which = 0 forward, 1 backward main stream (dgrads), 2 backward side stream (wgrads) */
+/* workspace of the layer's GEMMs (as peneo_gemm_workspace_bytes): which = 0 forward, 1 backward main stream (dgrads), 2 backward
+ * side stream (wgrads) */
 size_t peneo_encoder_layer_workspace_bytes(int rows, int H, int I, int which);
 int peneo_encoder_layer_fwd(const peneo_encoder_layer* layer, void* out, void* workspace, size_t workspace_bytes,
                             peneo_stream_t stream);
@@ -571,11 +578,11 @@ int peneo_spots_compact(const float* logits, int64_t P, int C, int N, int32_t* s
  * choice (default; also set by PENEO_GEMM_BIG), 256 / 384 / 128 = force one big-tile shape where its constraints hold.  A plain
  * global: set it while no peneo_gemm call is in flight on any thread.  Used by the kernel tests and tools/ only. */
 void peneo_gemm_set_big_mode(int mode);
-/* The same for the persistent stream-k launch (gemm_sk.hip; first choice of peneo_gemm for large bf16 problems with a k-major A):
- * 0 = off (the tiled kernels above), 1 = where the problem is large enough (default; also set by PENEO_GEMM_SK), 128 / 256 = force
- * the 256 x 128 / 256 x 256 tile wherever the kernel's constraints hold.  The launch keeps one fp32 slab per workgroup and a flag
- * word per workgroup in a buffer the library allocates per (device, stream) at the first call -- not during a stream capture: run
- * the captured sequence once eagerly first (a capture that meets a missing buffer falls back to the tiled kernels). */
+/* The same for the persistent launch (gemm_sk.hip; first choice of peneo_gemm for large bf16 problems with k-major A and B):
+ * 0 = off (the tiled kernels above), 1 = the measured rules (default; also set by PENEO_GEMM_SK), F * 1000 + BN = force ranges of
+ * whole 32 F x BN tiles, + 100000 = force ranges that cut tiles (stream-k), wherever the kernel's constraints hold (B k-major among
+ * them; elsewhere the tiled kernels run).  Instantiated tiles: F = 4 .. 8 with BN = 128, F = 4 .. 6 with BN = 256 (e.g. 5128, 4256,
+ * 105128); any other forced mode makes peneo_gemm return PENEO_ERR_INVALID.  Size workspaces under the mode they are used with. */
 void peneo_gemm_set_sk_mode(int mode);
 /* tools/ only.  peneo_gemm_sk_set_prof: device buffer of [1024][16] uint64 that receives one lane's s_memrealtime stamps (100 MHz) at
  * the stations of every workgroup's range of a persistent launch (0 start, 1 stream primed, 2 first unit landed, 3 / 4 slab publish,

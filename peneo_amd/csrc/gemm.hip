@@ -895,8 +895,9 @@ static int launch_gemm_dma_pipe(const GemmParams& p, bool ak, bool bk, dim3 grid
 using namespace peneo;
 
 extern "C" size_t peneo_gemm_workspace_bytes(int M, int N, int K, int split_k) {
-  (void)K;
-  return split_k > 1 ? (size_t)split_k * (size_t)M * (size_t)N * sizeof(float) : 0;
+  const size_t partials = split_k > 1 ? (size_t)split_k * (size_t)M * (size_t)N * sizeof(float) : 0;
+  const size_t stream_k = gemm_sk_workspace_bytes(M, N, K);
+  return partials > stream_k ? partials : stream_k;
 }
 
 extern "C" int peneo_gemm_group(int dtype, int a_kmajor, int b_kmajor, int c_dtype, const peneo_gemm_problem* problems, int n,
@@ -946,9 +947,11 @@ extern "C" int peneo_gemm_group(int dtype, int a_kmajor, int b_kmajor, int c_dty
   const bool ak = a_kmajor != 0, bk = b_kmajor != 0;
 #define PENEO_GROUP_LAUNCH(AK_, BK_)                                                                                         \
   {                                                                                                                          \
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_dma_pipe_group_kernel<AK_, BK_>),  \
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, shmem);                   \
-    if (attr != hipSuccess) { set_error("peneo_gemm_group: cannot raise dynamic LDS to %d bytes", shmem); return PENEO_ERR_LAUNCH; } \
+    static std::atomic<uint64_t> lds_devices{0};                                                                             \
+    if (!allow_dynamic_lds(reinterpret_cast<const void*>(gemm_dma_pipe_group_kernel<AK_, BK_>), shmem, lds_devices)) {       \
+      set_error("peneo_gemm_group: cannot raise dynamic LDS to %d bytes", shmem);                                            \
+      return PENEO_ERR_LAUNCH;                                                                                               \
+    }                                                                                                                        \
     hipLaunchKernelGGL((gemm_dma_pipe_group_kernel<AK_, BK_>), dim3((unsigned)tiles), dim3(256), shmem, st, g);              \
   }
   if (ak && bk) PENEO_GROUP_LAUNCH(true, true)
@@ -1015,7 +1018,7 @@ extern "C" int peneo_gemm(int dtype, int a_kmajor, int b_kmajor, int M, int N, i
     // (stream-k ranges), so a split the caller asked for is dropped with it; then the tiled 8-wave kernels
     GemmParams q = p;
     q.split_k = 1;
-    int big = launch_gemm_sk(q, b_kmajor != 0, st);
+    int big = launch_gemm_sk(q, b_kmajor != 0, workspace, workspace_bytes, st);
     if (big < 0) return big;
     if (big == 1) split_k = 1;
     if (big == 0) big = launch_gemm_big(p, b_kmajor != 0, st);

@@ -238,13 +238,10 @@ __global__ __launch_bounds__(512) void gemm_big_kernel(GemmParams p, int tiles_n
 template <typename C>
 static int launch_big(const GemmParams& p, hipStream_t st) {
   const int tm = (p.M + C::BM - 1) / C::BM, tn = (p.N + C::BN - 1) / C::BN;
-  static bool attr_done = false;
-  if (!attr_done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_big_kernel<C>), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES) != hipSuccess) {
-      set_error("peneo_gemm: cannot raise dynamic LDS to %d bytes", C::LDS_BYTES);
-      return PENEO_ERR_LAUNCH;
-    }
-    attr_done = true;
+  static std::atomic<uint64_t> lds_devices{0};
+  if (!allow_dynamic_lds(reinterpret_cast<const void*>(gemm_big_kernel<C>), C::LDS_BYTES, lds_devices)) {
+    set_error("peneo_gemm: cannot raise dynamic LDS to %d bytes", C::LDS_BYTES);
+    return PENEO_ERR_LAUNCH;
   }
   hipLaunchKernelGGL(gemm_big_kernel<C>, dim3((unsigned)(tm * tn)), dim3(512), C::LDS_BYTES, st, p, tn);
   const int rc = check_launch("peneo_gemm (big tiles)");

@@ -2,6 +2,7 @@
 // epilogue of peneo_gemm (bias, activation, pre-activation store, x act'(src), dropout, residual, fp32 accumulate) on 8
 // consecutive columns of one output row.
 #pragma once
+#include <atomic>
 #include "common.h"
 
 namespace peneo {
@@ -236,9 +237,23 @@ __device__ __forceinline__ void epilogue_store8(const GemmParams& p, int m, int 
 }
 
 
+// A kernel may use more dynamic LDS than the default only once that is set for it on the current device: set on its first
+// launch there.  `devices`: the kernel's own set of devices done (bit d = device d; a function-local static beside its launch).
+inline bool allow_dynamic_lds(const void* kernel, int bytes, std::atomic<uint64_t>& devices) {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return false;
+  const uint64_t bit = dev >= 0 && dev < 64 ? uint64_t(1) << dev : 0;
+  if (devices.load(std::memory_order_acquire) & bit) return true;
+  if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) return false;
+  devices.fetch_or(bit, std::memory_order_release);
+  return true;
+}
+
 // gemm_big.hip: 0 = the shape / options are not covered (the caller runs the 128 x 128 kernel), 1 = launched
 int launch_gemm_big(const GemmParams& p, bool b_kmajor, hipStream_t st);
-// gemm_sk.hip (persistent stream-k launch): same return convention
-int launch_gemm_sk(const GemmParams& p, bool b_kmajor, hipStream_t st);
+// gemm_sk.hip (persistent stream-k launch): same return convention.  A launch whose ranges cut tiles keeps its flags and slabs in
+// the caller's workspace (ws, ws_bytes): at least gemm_sk_workspace_bytes(M, N, K) bytes, 16-byte aligned.
+int launch_gemm_sk(const GemmParams& p, bool b_kmajor, void* ws, size_t ws_bytes, hipStream_t st);
+size_t gemm_sk_workspace_bytes(int M, int N, int K);
 
 }  // namespace peneo

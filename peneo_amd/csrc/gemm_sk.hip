@@ -22,16 +22,15 @@
 //     boundary is finished by the workgroup that holds its k = 0 piece; every other piece is the FIRST thing its workgroup
 //     computes, leaves as an fp32 slab in accumulator order (16-byte write-through stores; every wave drains its vm counter,
 //     barrier, one lane stores the flag) and is added by the finisher at the END of its range behind one relaxed poll + one
-//     agent-scope acquire (cdna guide, Guideline 16 recipe R1).  Flags are reset by their single consumer (a captured launch
-//     replays).  v is XCD-major, so the pieces of a tile sit on one XCD except at the seven seams.  Progress: a finisher waits
+//     agent-scope acquire (cdna guide, Guideline 16 recipe R1).  Flags and slabs live in the caller's workspace; the host zeroes
+//     the flags on the launch's stream right before every launch (the finisher's own reset of the flags it consumed is redundant
+//     with that).  v is XCD-major, so the pieces of a tile sit on one XCD except at the seven seams.  Progress: a finisher waits
 //     only for workgroups v + 1 .. v + 3, which publish before anything else, and an XCD dispatches its workgroups in id order.
 // Layouts: A k-major [M][K]; B k-major [N][K] (forward, x W^T); K % 64 == 0, N % 8 == 0, 16-byte aligned rows.
 // LDS image of a stage (gemm_big.hip's): rows of 128 B (64 k), A rows then B rows, pieces of 8 rows = one LDS-DMA instruction;
 // the 16-byte slot s of row r sits at s ^ ((r >> 1) & 7) (applied to the DMA source address, the destination is lane-linear):
 // every 16-lane group of a ds_read_b128 fragment read (16 rows x 32 k: lane = row + 16 x slot) covers all 16 bank slots.
 #include <cstdlib>
-#include <mutex>
-#include <unordered_map>
 #include <type_traits>
 #include "common.h"
 #include "gemm_common.h"
@@ -42,7 +41,7 @@ struct SkPlan {
   int tiles_n, tiles, ktiles, G;
   int cut;              // 1 = ranges of units (stream-k), 0 = ranges of whole tiles
   float* ws;            // [G] slabs of BM x BN floats (a workgroup's first piece when it is not the tile's k = 0 piece)
-  uint32_t* flags;      // [G] 0 = empty, 1 = slab published; reset by the finisher
+  uint32_t* flags;      // [G] 0 = empty, 1 = slab published; zeroed before every launch
   uint64_t* prof;       // tools only (peneo_gemm_sk_set_prof): [G][16] s_memrealtime stamps of one lane, or null
 };
 #define SK_STAMP(k) do { if (pl.prof && tid == 0) pl.prof[v * 16 + (k)] = wall_clock64(); } while (0)
@@ -393,14 +392,14 @@ __global__ __launch_bounds__(512) void gemm_sk_kernel(GemmParams p, SkPlan pl) {
 }
 
 // ---- host side ----
-struct SkWorkspace { float* ws = nullptr; uint32_t* flags = nullptr; size_t slab_floats = 0; int G = 0; };
-static std::mutex g_sk_mutex;
-static std::unordered_map<uint64_t, SkWorkspace> g_sk_ws;     // per (device, stream): launches of one stream are ordered
 static int g_sk_cus[64] = {};
 static uint64_t* g_sk_prof = nullptr;
 static int g_sk_max_g = 0;        // tools: cap on the workgroups of a launch (0 = one per CU)
+static int g_sk_mode = -1;        // PENEO_GEMM_SK: 0 = off, 1 = auto (default), else F * 1000 + BN (+ 100000: stream-k ranges)
 
-static int sk_cu_count(int dev) {
+static int sk_cu_count() {
+  int dev = 0;
+  (void)hipGetDevice(&dev);
   if (dev < 0 || dev >= 64) return 256;
   if (g_sk_cus[dev] == 0) {
     int n = 0;
@@ -410,63 +409,68 @@ static int sk_cu_count(int dev) {
   return g_sk_cus[dev];
 }
 
-// false = no workspace (allocation failed or a capture is in progress: the caller runs another kernel)
-static bool sk_workspace(int dev, hipStream_t st, int G, size_t slab_floats, SkWorkspace& out) {
-  std::lock_guard<std::mutex> lock(g_sk_mutex);
-  const uint64_t key = (reinterpret_cast<uint64_t>(st) << 6) ^ (uint64_t)dev;
-  SkWorkspace& w = g_sk_ws[key];
-  if (w.G < G || w.slab_floats < slab_floats) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) { (void)hipGetLastError(); return false; }
-    // the old slabs may still be read by a launch in flight on this stream
-    if (w.ws) { (void)hipStreamSynchronize(st); (void)hipFree(w.ws); (void)hipFree(w.flags); }
-    const int g = G > w.G ? G : w.G;
-    const size_t sf = slab_floats > w.slab_floats ? slab_floats : w.slab_floats;
-    w = SkWorkspace{};
-    float* ws = nullptr; uint32_t* fl = nullptr;
-    if (hipMalloc(&ws, (size_t)g * sf * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); return false; }
-    if (hipMalloc(&fl, 4096) != hipSuccess || hipMemset(fl, 0, 4096) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(ws); return false; }
-    w.ws = ws; w.flags = fl; w.G = g; w.slab_floats = sf;
-  }
-  out = w;
-  return true;
+static int sk_mode() {
+  if (g_sk_mode < 0) { const char* e = getenv("PENEO_GEMM_SK"); g_sk_mode = e ? atoi(e) : 1; }
+  return g_sk_mode;
 }
 
+// F * 1000 + BN (+ 100000: stream-k ranges) -> the tile and whether ranges cut tiles; false = no such tile is instantiated
+// (launch_sk_f below)
+static bool sk_decode(int mode, int& F, int& BN, bool& cut) {
+  cut = mode >= 100000;
+  const int m = cut ? mode - 100000 : mode;
+  F = m / 1000;
+  BN = m % 1000;
+  return (BN == 128 && F >= 4 && F <= 8) || (BN == 256 && F >= 4 && F <= 6);
+}
+
+// workgroups of a launch before a stream-k launch lowers them: one per CU, a multiple of 8, at most 1024 (and the tools' cap)
+static int sk_groups() {
+  int G = sk_cu_count() & ~7;
+  if (G > 1024) G = 1024;
+  if (g_sk_max_g > 0 && G > g_sk_max_g) G = g_sk_max_g & ~7;
+  return G;
+}
+
+// A stream-k launch of G workgroups keeps in the caller's workspace G flag words, then G slabs of BM x BN floats from the next
+// 256-byte boundary.  Sized for sk_groups(): the launch only ever lowers G.
+static size_t sk_flag_bytes(int G) { return ((size_t)G * sizeof(uint32_t) + 255) & ~(size_t)255; }
+static size_t sk_scratch_bytes(int G, int F, int BN) { return sk_flag_bytes(G) + (size_t)G * (32 * F) * BN * sizeof(float); }
+
+// ws: null = ranges of whole tiles; else ranges of units that cut tiles (stream-k), flags and slabs in `ws`
 template <typename C, int EP>
-static int launch_sk_ep(const GemmParams& p, bool cut, hipStream_t st) {
-  int dev = 0;
-  (void)hipGetDevice(&dev);
+static int launch_sk_ep(const GemmParams& p, void* ws, hipStream_t st) {
   SkPlan pl;
   const int tm = (p.M + C::BM - 1) / C::BM;
   pl.tiles_n = (p.N + C::BN - 1) / C::BN;
   pl.tiles = tm * pl.tiles_n;
   pl.ktiles = p.K / 64;
-  pl.cut = cut ? 1 : 0;
+  pl.cut = ws ? 1 : 0;
   const int64_t U = (int64_t)pl.tiles * pl.ktiles;
-  int G = sk_cu_count(dev) & ~7;
-  if (G > 1024) G = 1024;
-  if (g_sk_max_g > 0 && G > g_sk_max_g) G = g_sk_max_g & ~7;
+  int G = sk_groups();
   pl.ws = nullptr; pl.flags = nullptr;
-  if (cut) {
+  if (ws) {
     // every range holds at least a third of a tile's k-stages: a cut tile has at most three foreign pieces
     const int64_t min_units = (pl.ktiles + 2) / 3;
     while (G > 8 && U / G < min_units) G -= 8;
     if (U < G) return 0;
-    SkWorkspace w;
-    if (!sk_workspace(dev, st, G, C::SLAB_FLOATS, w)) return 0;
-    pl.ws = w.ws; pl.flags = w.flags;
+    pl.flags = static_cast<uint32_t*>(ws);
+    pl.ws = reinterpret_cast<float*>(static_cast<char*>(ws) + sk_flag_bytes(G));
   } else if (pl.tiles < G) {
     G = pl.tiles;
   }
   pl.G = G;
   pl.prof = g_sk_prof;
-  static bool attr_done = false;
-  if (!attr_done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_sk_kernel<C, EP>), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES) != hipSuccess) {
-      set_error("peneo_gemm: cannot raise dynamic LDS to %d bytes", C::LDS_BYTES);
-      return PENEO_ERR_LAUNCH;
-    }
-    attr_done = true;
+  static std::atomic<uint64_t> lds_devices{0};
+  if (!allow_dynamic_lds(reinterpret_cast<const void*>(gemm_sk_kernel<C, EP>), C::LDS_BYTES, lds_devices)) {
+    set_error("peneo_gemm: cannot raise dynamic LDS to %d bytes", C::LDS_BYTES);
+    return PENEO_ERR_LAUNCH;
+  }
+  // every flag the launch polls starts at 0 (under a stream capture: a memset node ahead of the kernel)
+  if (pl.flags && hipMemsetAsync(pl.flags, 0, (size_t)G * sizeof(uint32_t), st) != hipSuccess) {
+    (void)hipGetLastError();
+    set_error("peneo_gemm: cannot clear the stream-k flags");
+    return PENEO_ERR_LAUNCH;
   }
   hipLaunchKernelGGL((gemm_sk_kernel<C, EP>), dim3((unsigned)G), dim3(512), C::LDS_BYTES, st, p, pl);
   const int rc = check_launch("peneo_gemm (persistent)");
@@ -484,16 +488,16 @@ static int sk_ep_kind(const GemmParams& p) {
   return e.drop_p == 0.f ? SK_EP_BIAS : SK_EP_GENERIC;
 }
 template <typename C, bool FAST>
-static int launch_sk(const GemmParams& p, bool cut, hipStream_t st) {
+static int launch_sk(const GemmParams& p, void* ws, hipStream_t st) {
   if constexpr (FAST) {
     switch (sk_ep_kind(p)) {
-      case SK_EP_BIAS: return launch_sk_ep<C, SK_EP_BIAS>(p, cut, st);
-      case SK_EP_GELU: return launch_sk_ep<C, SK_EP_GELU>(p, cut, st);
-      case SK_EP_RES: return launch_sk_ep<C, SK_EP_RES>(p, cut, st);
+      case SK_EP_BIAS: return launch_sk_ep<C, SK_EP_BIAS>(p, ws, st);
+      case SK_EP_GELU: return launch_sk_ep<C, SK_EP_GELU>(p, ws, st);
+      case SK_EP_RES: return launch_sk_ep<C, SK_EP_RES>(p, ws, st);
       default: break;
     }
   }
-  return launch_sk_ep<C, SK_EP_GENERIC>(p, cut, st);
+  return launch_sk_ep<C, SK_EP_GENERIC>(p, ws, st);
 }
 
 // ring depth: as many stages as fit, at most 6
@@ -503,26 +507,46 @@ template <int F, int BN> struct SkPick {
   using type = SkCfg<F, BN, NS>;
 };
 
-static int g_sk_mode = -1;   // PENEO_GEMM_SK: 0 = off, 1 = auto (default), else F * 1000 + BN (+ 100000: stream-k ranges)
-
 // F = 7, 8 at N extent 256 are not instantiated: 112 / 128 accumulators + two k-halves of fragments + the batched epilogue do not
 // fit 256 registers (the compiler spills accumulators INSIDE the k loop: 230 us for a 20 GFLOP problem) and their 61 / 64 KiB
 // stages leave a two-stage ring (the fill queue drains at every stage: DESIGN 8)
 template <int BN>
-static int launch_sk_f(const GemmParams& p, int F, bool cut, hipStream_t st) {
+static int launch_sk_f(const GemmParams& p, int F, void* ws, hipStream_t st) {
   switch (F) {
-    case 4: return launch_sk<typename SkPick<4, BN>::type, BN == 256>(p, cut, st);
-    case 5: return launch_sk<typename SkPick<5, BN>::type, true>(p, cut, st);
-    case 6: return launch_sk<typename SkPick<6, BN>::type, false>(p, cut, st);
-    case 7: if constexpr (BN == 128) return launch_sk<typename SkPick<7, BN>::type, true>(p, cut, st); else return 0;
-    case 8: if constexpr (BN == 128) return launch_sk<typename SkPick<8, BN>::type, false>(p, cut, st); else return 0;
+    case 4: return launch_sk<typename SkPick<4, BN>::type, BN == 256>(p, ws, st);
+    case 5: return launch_sk<typename SkPick<5, BN>::type, true>(p, ws, st);
+    case 6: return launch_sk<typename SkPick<6, BN>::type, false>(p, ws, st);
+    case 7: if constexpr (BN == 128) return launch_sk<typename SkPick<7, BN>::type, true>(p, ws, st); else return 0;
+    case 8: if constexpr (BN == 128) return launch_sk<typename SkPick<8, BN>::type, false>(p, ws, st); else return 0;
     default: return 0;
   }
 }
 
-int launch_gemm_sk(const GemmParams& p, bool b_kmajor, hipStream_t st) {
-  if (g_sk_mode < 0) { const char* e = getenv("PENEO_GEMM_SK"); g_sk_mode = e ? atoi(e) : 1; }
-  if (g_sk_mode == 0 || !b_kmajor) return 0;
+static int64_t sk_tiles(int M, int N, int F, int BN) { return (int64_t)((M + 32 * F - 1) / (32 * F)) * ((N + BN - 1) / BN); }
+// the automatic choice leaves smaller problems to the 128 x 128 kernel, which fills the chip better there
+static bool sk_auto_large(int M, int N) { return (int64_t)M * N >= (int64_t)1 << 21 && M >= 256 && N >= 128; }
+// rule (3) of the automatic choice (few tiles x deep K: stream-k ranges on 160 x 128 tiles) for G = one workgroup per CU: the mode it
+// picks, or 0.  Also what sizes the workspace in auto mode (gemm_sk_workspace_bytes).
+static int sk_rule3(int M, int N, int K, int G) {
+  return sk_auto_large(M, N) && K >= 2048 && sk_tiles(M, N, 5, 128) * 10 <= (int64_t)G * 6 ? 105128 : 0;
+}
+
+size_t gemm_sk_workspace_bytes(int M, int N, int K) {
+  int mode = sk_mode(), F, BN;
+  bool cut;
+  if (mode == 1) mode = sk_rule3(M, N, K, sk_cu_count() & ~7);
+  return K % 64 == 0 && sk_decode(mode, F, BN, cut) && cut ? sk_scratch_bytes(sk_groups(), F, BN) : 0;
+}
+
+int launch_gemm_sk(const GemmParams& p, bool b_kmajor, void* ws, size_t ws_bytes, hipStream_t st) {
+  int mode = sk_mode(), F = 0, BN = 0;
+  bool cut = false;
+  if (mode == 0) return 0;
+  if (mode != 1 && !sk_decode(mode, F, BN, cut)) {
+    set_error("peneo_gemm: persistent GEMM mode %d names no instantiated tile (F * 1000 + N extent, + 100000 for stream-k ranges)", mode);
+    return PENEO_ERR_INVALID;
+  }
+  if (!b_kmajor) return 0;
   if (p.split_k > 1 || p.dz_on || p.K % 64 != 0 || p.K < 128 || p.N % 8 != 0) return 0;
   if ((reinterpret_cast<uintptr_t>(p.A) | reinterpret_cast<uintptr_t>(p.B)) & 15) return 0;
   if ((p.lda * 2) % 16 != 0 || (p.ldb * 2) % 16 != 0) return 0;
@@ -538,7 +562,6 @@ int launch_gemm_sk(const GemmParams& p, bool b_kmajor, hipStream_t st) {
   }
   // per-lane 32-bit offsets inside a tile
   if ((int64_t)256 * p.lda * 2 >= ((int64_t)1 << 31) || (int64_t)256 * p.ldb * 2 >= ((int64_t)1 << 31)) return 0;
-  int mode = g_sk_mode;
   if (mode == 1) {
     // The choice per problem (profiles/r06_gemm_persistent.txt).  One workgroup per CU has nothing to overlap a tile's epilogue
     // with, so at M = 5672 (no tile of the family fills a whole number of rounds there) the launch only ties the tiled kernels
@@ -549,11 +572,9 @@ int launch_gemm_sk(const GemmParams& p, bool b_kmajor, hipStream_t st) {
     //   (3) few tiles x deep K: stream-k ranges;
     // (2) and (3) only with one of the compact epilogues - with the generic one (56 - 142 KB of code) they lost inside the
     // large backbone's forward what they won alone.
-    if ((int64_t)p.M * p.N < (int64_t)1 << 21 || p.M < 256 || p.N < 128) return 0;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const int G = sk_cu_count(dev) & ~7;
-    auto tiles = [&](int F, int BN) { return (int64_t)((p.M + 32 * F - 1) / (32 * F)) * ((p.N + BN - 1) / BN); };
+    if (!sk_auto_large(p.M, p.N)) return 0;
+    const int G = sk_cu_count() & ~7;
+    auto tiles = [&](int F, int BN) { return sk_tiles(p.M, p.N, F, BN); };
     mode = 0;
     if (p.N >= 256 && tiles(4, 256) >= 3 * (int64_t)G) mode = 4256;
     else if (p.N < 256 && tiles(5, 128) >= 3 * (int64_t)G) mode = 5128;
@@ -571,16 +592,20 @@ int launch_gemm_sk(const GemmParams& p, bool b_kmajor, hipStream_t st) {
           const int pct = p.K > 1024 ? 90 : 84;
           if (p.N >= cand[c][1] && t <= (int64_t)k * G && t * 100 >= (int64_t)k * G * pct) mode = cand[c][0] * 1000 + cand[c][1];
         }
-      if (!mode && p.K >= 2048 && tiles(5, 128) * 10 <= (int64_t)G * 6) mode = 105128;
+      if (!mode) mode = sk_rule3(p.M, p.N, p.K, G);
     }
     if (!mode) return 0;
+    sk_decode(mode, F, BN, cut);
   }
-  const bool cut = mode >= 100000;
-  mode %= 100000;
-  const int F = mode / 1000, BN = mode % 1000;
-  if (BN == 256) return launch_sk_f<256>(p, F, cut, st);
-  if (BN == 128) return launch_sk_f<128>(p, F, cut, st);
-  return 0;
+  if (cut) {
+    const size_t need = sk_scratch_bytes(sk_groups(), F, BN);
+    if (!ws || ws_bytes < need || (reinterpret_cast<uintptr_t>(ws) & 15)) {
+      set_error("peneo_gemm: this stream-k launch needs a 16-byte aligned workspace of %zu bytes (peneo_gemm_workspace_bytes); got %zu bytes at %p",
+                need, ws_bytes, ws);
+      return PENEO_ERR_INVALID;
+    }
+  }
+  return BN == 256 ? launch_sk_f<256>(p, F, cut ? ws : nullptr, st) : launch_sk_f<128>(p, F, cut ? ws : nullptr, st);
 }
 
 }  // namespace peneo

@@ -33,9 +33,7 @@ size_t max2(size_t a, size_t b) { return a > b ? a : b; }
 struct Ws { void* p; size_t n; };
 int gemm(int ak, int bk, int M, int N, int K, const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc,
          int c_dtype, const peneo_gemm_epilogue& ep, Ws ws, hipStream_t st) {
-  const int split = auto_split(M, N, K);
-  return peneo_gemm(PENEO_BF16, ak, bk, M, N, K, A, lda, B, ldb, C, ldc, c_dtype, &ep, split, split > 1 ? ws.p : nullptr,
-                    split > 1 ? ws.n : 0, st);
+  return peneo_gemm(PENEO_BF16, ak, bk, M, N, K, A, lda, B, ldb, C, ldc, c_dtype, &ep, auto_split(M, N, K), ws.p, ws.n, st);
 }
 
 // two reusable events per (host thread, device) for the main -> side hand-offs of a backward (a wait captures the record that

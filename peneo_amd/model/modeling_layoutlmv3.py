@@ -288,14 +288,11 @@ class _EmbedStage(torch.autograd.Function):
 # schedule).  PENEO_STAGE_CALLS=0: the per-kernel sequence below (also what fp32 parity mode and the optional schedules run).
 # ------------------------------------------------------------------------------------------------
 STAGE_CALLS = os.environ.get("PENEO_STAGE_CALLS", "1") != "0"
-_WS_BYTES: dict = {}
 
 
 def _layer_ws_bytes(rows: int, H: int, I: int, which: int) -> int:
-    key = (rows, H, I, which)
-    if key not in _WS_BYTES:
-        _WS_BYTES[key] = int(hip_lib().peneo_encoder_layer_workspace_bytes(rows, H, I, which))
-    return _WS_BYTES[key]
+    # (not cached: the size follows the persistent GEMM mode, which the library may change between calls)
+    return int(hip_lib().peneo_encoder_layer_workspace_bytes(rows, H, I, which))
 
 
 def _use_stage_calls(model, st, H: int, I: int) -> bool:

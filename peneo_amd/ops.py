@@ -170,10 +170,9 @@ def gemm(a: torch.Tensor, b: torch.Tensor, *, a_kmajor: bool = True, b_kmajor: b
         split_k = 1
     if split_k is None:
         split_k = choose_split_k(M, N, K, a.dtype)
-    ws, ws_bytes = None, 0
-    if split_k > 1:
-        ws_bytes = lib().peneo_gemm_workspace_bytes(M, N, K, split_k)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=a.device)
+    # split-k partials, or the flags and slabs of a stream-k launch (which may need them with split_k == 1)
+    ws_bytes = lib().peneo_gemm_workspace_bytes(M, N, K, split_k)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=a.device) if ws_bytes else None
     check(lib().peneo_gemm(dtype_code(a.dtype), int(a_kmajor), int(b_kmajor), M, N, K, ptr(a), a.stride(0), ptr(b),
                            b.stride(0), ptr(out), out.stride(0), dtype_code(out.dtype), C.byref(ep), split_k, ptr(ws),
                            ws_bytes, stream()), "peneo_gemm")

@@ -809,8 +809,8 @@ def test_gemm_stream_k_matches_fp32_matmul(ops, mode, bk):
     range boundaries (few tiles x many k-stages), ranges of one unit, M / N that are no multiple of the tile, every fused epilogue
     option -- against an fp32 matmul of the same bf16 operands and
     against the 128 x 128 kernel (same dropout mask function, same epilogue arithmetic: only the summation order differs).
-    Every problem is launched three times with fresh operands: the slab flags are reset by their consumers, so a stale flag or a
-    stale slab from the launch before shows as a wrong tile."""
+    Every problem is launched three times with fresh operands: a stale flag or a stale slab from the launch before shows as a
+    wrong tile."""
     import ctypes
     from peneo_amd import hip
     lib = ctypes.CDLL(hip.LIB_PATH)
@@ -855,8 +855,8 @@ def test_gemm_stream_k_matches_fp32_matmul(ops, mode, bk):
 
 
 def test_gemm_stream_k_hand_off_under_uneven_load(ops):
-    """The stream-k slab hand-off (write-through slab stores, vm drain, flag; relaxed poll + one agent-scope acquire; flags reset by
-    their consumer) checked the way the CDNA guide asks for: every word of every result, many launches in a row with fresh operands
+    """The stream-k slab hand-off (write-through slab stores, vm drain, flag; relaxed poll + one agent-scope acquire; flags zeroed
+    ahead of every launch) checked the way the CDNA guide asks for: every word of every result, many launches in a row with fresh operands
     (a stale flag or a stale slab of the launch before shows), and beside a second stream that keeps part of the CUs busy with long
     workgroups, so that the ranges of a launch start at uneven times and a finisher meets slabs that are not there yet."""
     import ctypes
@@ -892,6 +892,80 @@ def test_gemm_stream_k_hand_off_under_uneven_load(ops):
             bad += int(not (err < 1e-2))
         torch.cuda.synchronize()
         assert bad == 0, f"{bad} of 60 stream-k launches differ from the tiled kernel"
+    finally:
+        lib.peneo_gemm_set_sk_mode(1)
+
+
+def test_gemm_stream_k_captured_equals_eager(ops):
+    """A stream-k launch captured into a graph on a fresh stream keeps its flags and slabs in the workspace the captured ops.gemm
+    allocated, behind a memset node that zeroes the flags: each of three replays with fresh operands copied into the static inputs
+    equals an eager launch on the same operands bit for bit, and the tiled kernel to bf16 noise."""
+    import ctypes
+    from peneo_amd import hip
+    lib = ctypes.CDLL(hip.LIB_PATH)
+    g = torch.Generator().manual_seed(31)
+    M, N, K = 1500, 768, 3072
+    dt = torch.bfloat16
+
+    def operands():
+        return (torch.randn(M, K, generator=g).to(DEV).to(dt), (torch.randn(N, K, generator=g) * 0.05).to(DEV).to(dt),
+                torch.randn(N, generator=g).to(DEV))
+
+    a_s, b_s, bias_s = operands()
+    try:
+        lib.peneo_gemm_set_sk_mode(105128)
+        ops.gemm(a_s, b_s, bias=bias_s, split_k=1)       # warm-up on the current stream, not on the capture stream
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, stream=torch.cuda.Stream()):
+            out_s = ops.gemm(a_s, b_s, bias=bias_s, split_k=1)
+        for rep in range(3):
+            a, b, bias = operands()
+            a_s.copy_(a)
+            b_s.copy_(b)
+            bias_s.copy_(bias)
+            graph.replay()
+            eager = ops.gemm(a, b, bias=bias, split_k=1)
+            lib.peneo_gemm_set_sk_mode(0)
+            tiled = ops.gemm(a, b, bias=bias, split_k=1)
+            lib.peneo_gemm_set_sk_mode(105128)
+            assert torch.equal(out_s, eager), rep
+            assert rel_err(out_s, tiled) < 1e-2, rep
+    finally:
+        lib.peneo_gemm_set_sk_mode(1)
+
+
+def test_gemm_stream_k_refuses_a_short_workspace_and_an_unknown_mode(ops):
+    """A forced stream-k launch given a null workspace, one a byte smaller than peneo_gemm_workspace_bytes or a misaligned one, and
+    a forced mode that names no instantiated tile: peneo_gemm returns PENEO_ERR_INVALID instead of allocating or running the tiled
+    kernels, and launches nothing (C keeps its sentinel)."""
+    import ctypes
+    from peneo_amd import hip
+    lib = hip.lib()
+    M, N, K = 1500, 768, 3072
+    a = torch.ones(M, K, dtype=torch.bfloat16, device=DEV)
+    b = torch.ones(N, K, dtype=torch.bfloat16, device=DEV)
+    c = torch.full((M, N), 7.0, dtype=torch.bfloat16, device=DEV)
+    ep = hip.GemmEpilogue()
+
+    def call(ws_ptr, ws_bytes):
+        return lib.peneo_gemm(hip.BF16, 1, 1, M, N, K, a.data_ptr(), K, b.data_ptr(), K, c.data_ptr(), N, hip.BF16, ctypes.byref(ep),
+                              1, ws_ptr, ws_bytes, hip.stream())
+
+    try:
+        lib.peneo_gemm_set_sk_mode(105128)
+        need = lib.peneo_gemm_workspace_bytes(M, N, K, 1)
+        assert need > 0
+        ws = torch.empty(need + 64, dtype=torch.uint8, device=DEV)
+        for ws_ptr, ws_bytes in [(None, 0), (ws.data_ptr(), need - 1), (ws.data_ptr() + 8, need)]:
+            assert call(ws_ptr, ws_bytes) == -1
+            assert b"workspace" in lib.peneo_last_error()
+        lib.peneo_gemm_set_sk_mode(3128)
+        assert lib.peneo_gemm_workspace_bytes(M, N, K, 1) == 0
+        assert call(ws.data_ptr(), need) == -1
+        assert b"3128" in lib.peneo_last_error()
+        torch.cuda.synchronize()
+        assert bool((c == 7.0).all())
     finally:
         lib.peneo_gemm_set_sk_mode(1)
 

@@ -58,6 +58,32 @@ def test_fused_pair_backward_query_knows_the_lds_limit():
     assert f(F32, 384, 5) == 0 and f(BF16, 400, 5) == 0
 
 
+def test_gemm_workspace_holds_the_stream_k_scratch():
+    """peneo_gemm_workspace_bytes (a host-side question) covers what a persistent launch whose ranges cut tiles keeps in the caller's
+    workspace under the current mode -- G flag words padded to 256 bytes, then G slabs of BM x BN floats, G = one workgroup per CU
+    (256 where no device answers) -- with split_k == 1 too, and is the split-k partials alone where no such launch can run."""
+    from peneo_amd import hip
+    lib = hip.load_library()
+    ws = lib.peneo_gemm_workspace_bytes
+    G = (torch.cuda.get_device_properties(0).multi_processor_count if torch.cuda.is_available() else 256) // 8 * 8
+    try:
+        lib.peneo_gemm_set_sk_mode(105128)
+        assert ws(1500, 768, 3072, 1) == 1024 + G * 160 * 128 * 4
+        assert ws(1500, 768, 3000, 1) == 0                                  # K % 64 != 0: no persistent launch
+        lib.peneo_gemm_set_sk_mode(104256)
+        assert ws(1500, 768, 3072, 1) == ws(1500, 768, 3072, 2) == 1024 + G * 128 * 256 * 4
+        assert ws(1500, 768, 3072, 16) == 16 * 1500 * 768 * 4               # the larger of the two
+        lib.peneo_gemm_set_sk_mode(1)                                         # rule (3): few tiles x deep K
+        assert ws(2442, 1024, 4096, 1) == 1024 + G * 160 * 128 * 4
+        assert ws(5672, 768, 768, 1) == 0 and ws(1500, 768, 3072, 1) == 0
+        for mode in (0, 5128, 3128, 103128):                                  # off, whole tiles, no such tile
+            lib.peneo_gemm_set_sk_mode(mode)
+            assert ws(2442, 1024, 4096, 1) == 0
+            assert ws(768, 768, 5672, 8) == 8 * 768 * 768 * 4
+    finally:
+        lib.peneo_gemm_set_sk_mode(1)
+
+
 def test_no_cpu_fallback():
     from peneo_amd import ops
     from peneo_amd.hip import PeneoHipError
