@@ -375,6 +375,33 @@ int peneo_pair_heads_fwd_save(int dtype, const void* ab, int B, int N, const pen
                               float* const* logits, const peneo_pair_loss* loss, void* act, void* x_rows,
                               peneo_stream_t stream);
 
+/* MXFP8 inference form of the same heads (pair_heads_mx.hip; eval only: no dropout, no dlogits, no backward).
+ * Both first-layer operands, the rows of W1cat [num_heads * D, D] and every pair's x = SiLU(a_i + b_j) (fp32 from the bf16 `ab`),
+ * are quantized to OCP MX v1.0 MXFP8: per block of 32 consecutive elements along D, scale 2^e with e = floor(log2(amax)) - 8
+ * clamped to the E8M0 range [-127, 127] (an all-zero block: e = -127), elements e4m3fn(RNE(clamp(v / 2^e, -448, 448))).
+ * z = W1_h x accumulates in fp32 on the block-scaled MFMA (v_mfma_scale_f32_32x32x64_f8f6f4); + b1, SiLU, then the second layer and
+ * the loss of peneo_pair_heads_fwd (y as bf16, W2 bf16, fp32 accumulate, + b2).  256 pairs per workgroup as there:
+ * `loss->partials` has peneo_pair_loss_partials(B, N) rows.
+ *
+ * peneo_mxfp8_quantize_rows: src [rows, cols] fp32 row-major (cols % 32 == 0, 16-byte aligned) -> q [rows, cols] e4m3 bytes and
+ * scales [rows, cols / 32] E8M0 bytes, both caller-owned; the quantizer the pack and the kernel apply.
+ * peneo_pair_mxfp8_supported: host-side query (no GPU call): 1 when D % 64 == 0, 64 <= D <= 512, 1 <= num_heads <= PENEO_MAX_HEADS
+ * and the weight ring fits in LDS, else 0.
+ * peneo_pair_heads_pack_mxfp8: w1 / w2 / classes as for peneo_pair_heads_pack -> `packed` [peneo_pair_heads_mxfp8_packed_bytes]
+ * (16-byte aligned; 0 bytes = unsupported shape): per 32-row slab the e4m3 first-layer fragments, their E8M0 scales and the bf16
+ * second-layer fragments, in fragment order.  Once per weight version.
+ * peneo_pair_heads_fwd_mxfp8: ab [B, N, 2D] bf16; `desc` as for peneo_pair_heads_fwd with w_packed from the pack above and
+ * drop_p == 0; `loss` (may be NULL) with every dlogits[h] NULL.  Other arguments give PENEO_ERR_INVALID. */
+int peneo_mxfp8_quantize_rows(const float* src, int64_t rows, int64_t cols, void* q_e4m3, void* scales_e8m0,
+                              peneo_stream_t stream);
+int peneo_pair_mxfp8_supported(int D, int num_heads);
+size_t peneo_pair_heads_mxfp8_packed_bytes(int num_heads, int D);
+int peneo_pair_heads_pack_mxfp8(const float* const* w1, const float* const* w2, const int* classes, int num_heads, int D,
+                                void* packed, peneo_stream_t stream);
+int peneo_pair_heads_fwd_mxfp8(const void* ab, int B, int N, const peneo_pair_heads_desc* desc,
+                               float* const* logits /* host array of num_heads device pointers, or NULL */,
+                               const peneo_pair_loss* loss, peneo_stream_t stream);
+
 /* --- building blocks of the chunked backward (rows i0..i1 of the pair triangle = pairs
  *     p(i0,i0) .. p(i1,i1)-1 of one document) ------------------------------------------- */
 /* x[p - p0, :] = SiLU(a_i + b_j)  [npairs, D];  pre (may be NULL) receives a_i + b_j itself, the `grad_src` that lets the

@@ -1,0 +1,470 @@
+// MXFP8 eval path of the five pair-classifier heads (K11 + K12 + K13 forward, no dropout, no backward).
+//
+// Same skeleton as pair_heads_fwd_kernel (pair_heads.hip): one workgroup owns 256 consecutive pairs of one document, each
+// 64-lane wave 32 of them (lane & 31 = pair); x = SiLU(a_i + b_j) stays in B-operand registers for the whole launch; the
+// first-layer weights of all heads stream L2 -> LDS by LDS-DMA, one 32-row slab of hidden units at a time, through a ring of
+// NSTAGE buffers; the C-layout accumulator of a slab is, after bias + SiLU, the B operand of the bf16 second layer.  The first
+// layer runs on v_mfma_scale_f32_32x32x64_f8f6f4 with OCP e4m3 operands and E8M0 block scales (OCP MX v1.0, blocks of 32
+// consecutive elements along D): twice the bf16 MFMA rate, half the weight bytes per slab, half the x registers.
+//
+// Operand maps of the scaled MFMA with e4m3 operands (checked on the MI355X with exact integer data and random scales):
+//   A: lane l holds row l & 31; byte j (0..31) of its 8 dwords is k = 32 (j >> 4) + 16 (l >> 5) + (j & 15) of the 64-wide step
+//   B: lane l holds column l & 31, bytes as for A
+//   scales: the op_sel byte of lane r + 32 kb's scale VGPR scales row (column) r, K-block kb = k / 32 of the step
+// so one 32-element block of a pair is spread over two lanes (16 elements in lane c, 16 in lane c + 32): its amax takes one
+// cross-half exchange.  The C/D map is that of every 32x32 MFMA (common.h acc_row).
+//
+// Quantization (both operands of the first layer, the pack and peneo_mxfp8_quantize_rows alike): for a block with amax > 0 the
+// scale is 2^e, e = floor(log2(amax)) - 8 clamped to [-127, 127] (E8M0 byte e + 127; an all-zero block gets byte 0); an element
+// becomes e4m3fn(RNE(clamp(v / 2^e, -448, 448))).  v / 2^e is an exact power-of-two multiply; v_cvt_pk_fp8_f32 rounds to nearest
+// even with e4m3 subnormals but returns NaN above 464 instead of saturating (measured), hence the explicit clamp.
+#include <stdlib.h>
+#include <type_traits>
+
+#include "common.h"
+
+namespace peneo {
+namespace {
+
+constexpr int MX_WAVES = 8;
+constexpr int MX_PAIRS = MX_WAVES * 32;   // as PH_PAIRS: the loss partial rows are peneo_pair_loss_partials(B, N)
+constexpr int MX_NCP = 16;
+constexpr int MX_MAX_KS = 8;              // D <= 512 (x: D / 8 VGPRs per lane)
+constexpr float NEG_INF_MX = -3.0e38f;
+typedef int i32x8_t __attribute__((ext_vector_type(8)));
+
+// Packed slab (32 hidden rows of W1cat, 16-byte aligned parts):
+//   KS8 = D / 64 first-layer fragments of 2 KiB: byte (c * 1024 + lane * 16 + t) of fragment ks =
+//        e4m3(W1cat[slab * 32 + (lane & 31)][64 ks + 32 c + 16 (lane >> 5) + t])        (c = K-block of the step, t = 0..15)
+//   NSW = ceil(KS8 / 4) scale words of 256 B: byte (ks & 3) of word [ks >> 2][lane] = E8M0 of row slab * 32 + (lane & 31),
+//        block 2 ks + (lane >> 5)
+//   2 bf16 second-layer fragments of 1 KiB (the bf16 pack's fragments KS, KS + 1: pack_weights_kernel)
+// padded to a whole number of 1 KiB DMA pieces per wave.
+__host__ __device__ constexpr int mx_scale_words(int ks8) { return (ks8 + 3) / 4; }
+__host__ __device__ constexpr int mx_payload(int ks8) { return ks8 * 2048 + mx_scale_words(ks8) * 256 + 2048; }
+__host__ __device__ constexpr int mx_upw(int ks8) { return (mx_payload(ks8) + MX_WAVES * 1024 - 1) / (MX_WAVES * 1024); }
+__host__ __device__ constexpr int mx_slab_bytes(int ks8) { return mx_upw(ks8) * MX_WAVES * 1024; }
+// ring depth: 3 while two workgroups still fit a CU's 160 KiB of LDS, else 2
+__host__ __device__ constexpr int mx_nstage(int ks8) { return ks8 <= 6 ? 3 : 2; }
+
+// E8M0 byte of a block with maximum magnitude amax (>= 0): max(floor(log2 amax) - 8, -127) + 127, read off the exponent field
+__device__ __forceinline__ uint32_t mx_scale_byte(float amax) {
+  const int e = (int)((__float_as_uint(amax) >> 23) & 255u) - 8;
+  return (uint32_t)(e < 0 ? 0 : e);
+}
+// 1 / 2^(byte - 127), exact (byte <= 247)
+__device__ __forceinline__ float mx_inv_scale(uint32_t byte) { return __uint_as_float((254u - byte) << 23); }
+// four values (already divided by the block scale) -> four e4m3 bytes, little-endian in order
+__device__ __forceinline__ uint32_t mx_e4m3x4(float v0, float v1, float v2, float v3) {
+  v0 = fminf(fmaxf(v0, -448.f), 448.f); v1 = fminf(fmaxf(v1, -448.f), 448.f);
+  v2 = fminf(fmaxf(v2, -448.f), 448.f); v3 = fminf(fmaxf(v3, -448.f), 448.f);
+  int w = __builtin_amdgcn_cvt_pk_fp8_f32(v0, v1, 0, false);
+  w = __builtin_amdgcn_cvt_pk_fp8_f32(v2, v3, w, true);
+  return (uint32_t)w;
+}
+// one block of 32 values -> 8 dwords of e4m3 + its E8M0 byte
+__device__ __forceinline__ uint32_t mx_quantize32(const float (&v)[32], uint32_t (&q)[8]) {
+  float amax = 0.f;
+#pragma unroll
+  for (int t = 0; t < 32; ++t) amax = fmaxf(amax, fabsf(v[t]));
+  const uint32_t sb = mx_scale_byte(amax);
+  const float inv = mx_inv_scale(sb);
+#pragma unroll
+  for (int w = 0; w < 8; ++w) q[w] = mx_e4m3x4(v[4 * w] * inv, v[4 * w + 1] * inv, v[4 * w + 2] * inv, v[4 * w + 3] * inv);
+  return sb;
+}
+
+__global__ __launch_bounds__(256) void mx_quantize_rows_kernel(const float* src, int64_t nblocks, uint8_t* q, uint8_t* sc) {
+  for (int64_t blk = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; blk < nblocks; blk += (int64_t)gridDim.x * blockDim.x) {
+    float v[32];
+    const float4* s4 = reinterpret_cast<const float4*>(src + blk * 32);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) { const float4 f = s4[i]; v[4 * i] = f.x; v[4 * i + 1] = f.y; v[4 * i + 2] = f.z; v[4 * i + 3] = f.w; }
+    uint32_t w[8];
+    sc[blk] = (uint8_t)mx_quantize32(v, w);
+    uint4* d4 = reinterpret_cast<uint4*>(q + blk * 32);
+    d4[0] = make_uint4(w[0], w[1], w[2], w[3]);
+    d4[1] = make_uint4(w[4], w[5], w[6], w[7]);
+  }
+}
+
+struct MxPackSrc {
+  const float* w1[PENEO_MAX_HEADS];
+  const float* w2[PENEO_MAX_HEADS];
+  int classes[PENEO_MAX_HEADS];
+  int num_heads, D;
+};
+
+// first layer: one thread per (row of W1cat, 32-element block); the buffer has been zeroed (padding, unused scale bytes)
+__global__ __launch_bounds__(256) void mx_pack_w1_kernel(MxPackSrc s, char* out) {
+  const int D = s.D, ks8 = D / 64, nblk = D / 32;
+  const int64_t total = (int64_t)s.num_heads * D * nblk;
+  const int64_t slab_bytes = mx_slab_bytes(ks8);
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int row = (int)(i / nblk), kb = (int)(i % nblk);
+    const int h = row / D;
+    const float* src = s.w1[h] + (int64_t)(row - h * D) * D + 32 * kb;
+    float v[32];
+#pragma unroll
+    for (int t = 0; t < 32; ++t) v[t] = src[t];
+    uint32_t w[8];
+    const uint32_t sb = mx_quantize32(v, w);
+    char* slab = out + (int64_t)(row >> 5) * slab_bytes;
+    const int ks = kb >> 1, c = kb & 1, r = row & 31;
+#pragma unroll
+    for (int hh = 0; hh < 2; ++hh)   // elements 16 hh .. 16 hh + 15 of the block sit in lane r + 32 hh
+      *reinterpret_cast<uint4*>(slab + ks * 2048 + c * 1024 + (r + 32 * hh) * 16) = make_uint4(w[4 * hh], w[4 * hh + 1], w[4 * hh + 2], w[4 * hh + 3]);
+    slab[ks8 * 2048 + (ks >> 2) * 256 + (r + 32 * c) * 4 + (ks & 3)] = (char)sb;
+  }
+}
+
+// second layer: the bf16 pack's two W2 fragments per slab (pack_weights_kernel, fragments KS and KS + 1)
+__global__ __launch_bounds__(256) void mx_pack_w2_kernel(MxPackSrc s, char* out) {
+  const int D = s.D, ks8 = D / 64;
+  const int nslab = s.num_heads * D / 32;
+  const int64_t slab_bytes = mx_slab_bytes(ks8);
+  const int64_t total = (int64_t)nslab * 2 * 64 * 8;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int e = (int)(i & 7), lane = (int)((i >> 3) & 63), kk = (int)((i >> 9) & 1), slab = (int)(i >> 10);
+    const int cls = lane & 31;
+    const int hidden = slab * 32 + 16 * kk + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
+    const int h = hidden / D;
+    int off = 0;
+    for (int q = 0; q < h; ++q) off += s.classes[q];
+    float v = 0.f;
+    if (cls >= off && cls < off + s.classes[h]) v = s.w2[h][(int64_t)(cls - off) * D + (hidden - h * D)];
+    bf16_t* dst = reinterpret_cast<bf16_t*>(out + slab * slab_bytes + ks8 * 2048 + mx_scale_words(ks8) * 256 + kk * 1024 + lane * 16);
+    dst[e] = f32_to_bf16(v);
+  }
+}
+
+struct MxFwdParams {
+  const bf16_t* ab; int B, N, D; int64_t P;
+  int num_heads; int classes[PENEO_MAX_HEADS];
+  const char* wp; const float* b1; const float* b2;
+  float* logits[PENEO_MAX_HEADS];
+  const int64_t* tags[PENEO_MAX_HEADS];
+  const float* cw[PENEO_MAX_HEADS];
+  float* partials;   // [B * gridDim.x][32]: num[8] | den[8] | dl_sum[16] per workgroup (peneo_loss_finish)
+};
+
+template <int I, int N, typename F>
+__device__ __forceinline__ void mx_static_for(F&& f) {
+  if constexpr (I < N) { f(std::integral_constant<int, I>{}); mx_static_for<I + 1, N>(f); }
+}
+__device__ __forceinline__ float mx_cls_at(const float (&cls)[MX_NCP], int idx) {
+  float v = 0.f;
+#pragma unroll
+  for (int c = 0; c < MX_NCP; ++c) v = (c == idx) ? cls[c] : v;
+  return v;
+}
+
+// logits^T accumulator -> per-pair logits and the class-weighted CE partial row of the workgroup (the bf16 kernel's epilogue
+// without dropout scale and dlogits stores; dl_sum is still summed, so peneo_loss_finish reads the same row format)
+__device__ __forceinline__ void mx_epilogue(const MxFwdParams& p, const f32x16_t& lg, char* smem, int tid, int lane, int wave,
+                                            int half, int b, int64_t mypair, bool pair_ok) {
+  float mine[8], other[8];
+#pragma unroll
+  for (int r = 0; r < 8; ++r) { mine[r] = lg[r]; other[r] = __shfl_xor(lg[r], 32, 64); }
+  float cls[MX_NCP];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    cls[c] = half == 0 ? mine[c] : other[c];
+    cls[4 + c] = half == 0 ? other[c] : mine[c];
+    cls[8 + c] = half == 0 ? mine[4 + c] : other[4 + c];
+    cls[12 + c] = half == 0 ? other[4 + c] : mine[4 + c];
+  }
+  float num[PENEO_MAX_HEADS], den[PENEO_MAX_HEADS], dls[MX_NCP];
+#pragma unroll
+  for (int h = 0; h < PENEO_MAX_HEADS; ++h) { num[h] = 0.f; den[h] = 0.f; }
+#pragma unroll
+  for (int c = 0; c < MX_NCP; ++c) dls[c] = 0.f;
+  const bool writer = pair_ok && half == 0;
+  int off = 0;
+#pragma unroll
+  for (int h = 0; h < PENEO_MAX_HEADS; ++h) {
+    if (h < p.num_heads) {
+      const int C = p.classes[h];
+      float l[4];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) l[c] = (c < C) ? mx_cls_at(cls, off + c) + p.b2[off + c] : NEG_INF_MX;
+      if (writer && p.logits[h]) {
+        float* dst = p.logits[h] + ((int64_t)b * p.P + mypair) * C;
+        for (int c = 0; c < C; ++c) dst[c] = l[c];
+      }
+      if (writer && p.tags[h]) {
+        const int tag = (int)p.tags[h][(int64_t)b * p.P + mypair];
+        const float mx = fmaxf(fmaxf(l[0], l[1]), fmaxf(l[2], l[3]));
+        float e[4], se = 0.f;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) { e[c] = (c < C) ? __expf(l[c] - mx) : 0.f; se += e[c]; }
+        const float lse = mx + __logf(se);
+        float lt = 0.f;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) lt = (c == tag) ? l[c] : lt;
+        const float w = (tag < 0 || tag >= C) ? 0.f : (p.cw[h] ? p.cw[h][tag] : 1.f);
+        num[h] = w * (lse - lt);
+        den[h] = w;
+        const float inv = 1.f / se;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const float g = (c < C) ? w * (e[c] * inv - (c == tag ? 1.f : 0.f)) : 0.f;
+#pragma unroll
+          for (int q = 0; q < MX_NCP; ++q) dls[q] += (q == off + c) ? g : 0.f;
+        }
+      }
+      off += C;
+    }
+  }
+  if (p.partials) {
+    float* sRed = reinterpret_cast<float*>(smem);  // [8 waves][32] (the weight ring is dead)
+    __syncthreads();
+#pragma unroll
+    for (int h = 0; h < PENEO_MAX_HEADS; ++h) {
+      const float a = wave_sum(num[h]), d2 = wave_sum(den[h]);
+      if (lane == 0) { sRed[wave * 32 + h] = a; sRed[wave * 32 + 8 + h] = d2; }
+    }
+#pragma unroll
+    for (int c = 0; c < MX_NCP; ++c) {
+      const float a = wave_sum(dls[c]);
+      if (lane == 0) sRed[wave * 32 + 16 + c] = a;
+    }
+    __syncthreads();
+    if (tid < 32) {
+      float t = 0.f;
+#pragma unroll
+      for (int w = 0; w < MX_WAVES; ++w) t += sRed[w * 32 + tid];
+      p.partials[((int64_t)b * gridDim.x + blockIdx.x) * 32 + tid] = t;
+    }
+  }
+}
+
+template <int KS8, int NSTAGE>
+__global__ __launch_bounds__(MX_WAVES * 64, 2) void pair_heads_mx_fwd_kernel(MxFwdParams p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int NSW = mx_scale_words(KS8), UPW = mx_upw(KS8), SLAB = mx_slab_bytes(KS8);
+  constexpr int D = KS8 * 64;
+  static_assert(UPW <= 12, "slab too large");
+  char* sW = smem;                                                    // [NSTAGE][SLAB]
+  float* sB1 = reinterpret_cast<float*>(smem + NSTAGE * SLAB);        // [nh * D]
+  const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int N = p.N, b = blockIdx.y;
+  const int64_t mypair = (int64_t)blockIdx.x * MX_PAIRS + wave * 32 + (lane & 31);
+  const bool pair_ok = mypair < p.P;
+  int pi, pj;
+  pair_decode(pair_ok ? mypair : p.P - 1, N, pi, pj);
+  const int nslab = p.num_heads * D / 32;
+
+  for (int i = tid; i < p.num_heads * D; i += MX_WAVES * 64) sB1[i] = p.b1[i];
+
+  // ---- x = SiLU(a_i + b_j), quantized to MXFP8 straight into B-operand registers: lane (c, half) of k-step ks holds
+  //      k = 64 ks + 32 kb + 16 half + t (kb = 0, 1; t = 0..15); block kb's amax meets its other 16 elements in lane ^ 32,
+  //      and this lane provides the scale of block kb = half ----
+  const bf16_t* abd = p.ab + (int64_t)b * N * 2 * D;
+  const bf16_t* arow = abd + (int64_t)pi * 2 * D;
+  const bf16_t* brow = abd + (int64_t)pj * 2 * D + D;
+  i32x8_t xf[KS8];
+  uint32_t xs[NSW];
+#pragma unroll
+  for (int g = 0; g < NSW; ++g) xs[g] = 0u;
+#pragma unroll
+  for (int ks = 0; ks < KS8; ++ks) {
+    float v[2][16];
+    float am[2];
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb) {
+      const int c = 64 * ks + 32 * kb + 16 * half;
+      float a[16], bb[16];
+      unpack16<bf16_t>(*reinterpret_cast<const uint4*>(arow + c), a);
+      unpack16<bf16_t>(*reinterpret_cast<const uint4*>(arow + c + 8), a + 8);
+      unpack16<bf16_t>(*reinterpret_cast<const uint4*>(brow + c), bb);
+      unpack16<bf16_t>(*reinterpret_cast<const uint4*>(brow + c + 8), bb + 8);
+      float m = 0.f;
+#pragma unroll
+      for (int t = 0; t < 16; ++t) { v[kb][t] = silu_f(a[t] + bb[t]); m = fmaxf(m, fabsf(v[kb][t])); }
+      am[kb] = fmaxf(m, __shfl_xor(m, 32, 64));
+    }
+    uint32_t q[8];
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb) {
+      const uint32_t sb = mx_scale_byte(am[kb]);
+      const float inv = mx_inv_scale(sb);
+#pragma unroll
+      for (int w = 0; w < 4; ++w)
+        q[4 * kb + w] = mx_e4m3x4(v[kb][4 * w] * inv, v[kb][4 * w + 1] * inv, v[kb][4 * w + 2] * inv, v[kb][4 * w + 3] * inv);
+      if (kb == half) xs[ks >> 2] |= sb << (8 * (ks & 3));
+    }
+#pragma unroll
+    for (int w = 0; w < 8; ++w) xf[ks][w] = (int)q[w];
+    __builtin_amdgcn_sched_barrier(0);   // few gathers in flight at a time (else their raw data spills)
+  }
+  // every ordinary global load above has been consumed: from here on the vm counter only sees our DMA pieces
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();   // sB1 visible
+
+  const char* wsrc = p.wp + wave * (UPW * 1024) + lane * 16;
+  const uint32_t wdst = lds_addr(sW) + wave * (UPW * 1024);
+#pragma unroll
+  for (int s0 = 0; s0 < NSTAGE - 1; ++s0)
+    if (s0 < nslab) lds_dma_units<0, UPW>(wsrc + (int64_t)s0 * SLAB, wdst + s0 * SLAB);
+
+  f32x16_t lg;   // logits^T[class, pair]
+#pragma unroll
+  for (int r = 0; r < 16; ++r) lg[r] = 0.f;
+
+  for (int slab = 0; slab < nslab; ++slab) {
+    // slabs slab .. slab + NSTAGE - 2 are in flight (fewer at the end): wait for the oldest, then publish it
+    if (NSTAGE > 2 && slab + 1 < nslab) wait_vm<(NSTAGE - 2) * UPW>(); else wait_vm<0>();
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+    if (slab + NSTAGE - 1 < nslab) lds_dma_units<0, UPW>(wsrc + (int64_t)(slab + NSTAGE - 1) * SLAB, wdst + ((slab + NSTAGE - 1) % NSTAGE) * SLAB);
+    const char* wb = sW + (slab % NSTAGE) * SLAB;
+    uint32_t ws[NSW];
+#pragma unroll
+    for (int g = 0; g < NSW; ++g) ws[g] = *reinterpret_cast<const uint32_t*>(wb + KS8 * 2048 + g * 256 + lane * 4);
+    f32x16_t z;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) z[r] = 0.f;
+    mx_static_for<0, KS8>([&](auto kc) {
+      constexpr int ks = decltype(kc)::value;
+      const uint4 lo = *reinterpret_cast<const uint4*>(wb + ks * 2048 + lane * 16);
+      const uint4 hi = *reinterpret_cast<const uint4*>(wb + ks * 2048 + 1024 + lane * 16);
+      const i32x8_t wf = {(int)lo.x, (int)lo.y, (int)lo.z, (int)lo.w, (int)hi.x, (int)hi.y, (int)hi.z, (int)hi.w};
+      z = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wf, xf[ks], z, 0, 0, ks & 3, (int)ws[ks >> 2], ks & 3, (int)xs[ks >> 2]);
+      // D = 512: x takes 64 VGPRs; with every fragment read of the slab hoisted to its top (16 VGPRs each) the kernel spills
+      if constexpr (KS8 > 6 && (ks & 1) == 1) __builtin_amdgcn_sched_barrier(0);
+    });
+    // bias + SiLU in registers; accumulator rows 8g + 4 half + 0..3 are the second layer's B operand (pack order)
+    float y[16];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const float4 bv = *reinterpret_cast<const float4*>(sB1 + slab * 32 + 8 * g + 4 * half);
+      y[4 * g + 0] = silu_f(z[4 * g + 0] + bv.x);
+      y[4 * g + 1] = silu_f(z[4 * g + 1] + bv.y);
+      y[4 * g + 2] = silu_f(z[4 * g + 2] + bv.z);
+      y[4 * g + 3] = silu_f(z[4 * g + 3] + bv.w);
+    }
+    const char* w2 = wb + KS8 * 2048 + NSW * 256;
+    Frag<bf16_t> w2a = load_frag_linear<bf16_t>(w2, 0, lane), w2b = load_frag_linear<bf16_t>(w2, 1, lane);
+    mma_step(w2a, pack_frag8<bf16_t>(y), lg);
+    mma_step(w2b, pack_frag8<bf16_t>(y + 8), lg);
+  }
+  mx_epilogue(p, lg, smem, tid, lane, wave, half, b, mypair, pair_ok);
+}
+
+template <int KS8>
+int launch_mx_fwd(const MxFwdParams& p, hipStream_t st) {
+  constexpr int NSTAGE = mx_nstage(KS8);
+  size_t sh = (size_t)NSTAGE * mx_slab_bytes(KS8) + (size_t)p.num_heads * p.D * sizeof(float);
+  if (sh < (size_t)MX_WAVES * 32 * sizeof(float)) sh = (size_t)MX_WAVES * 32 * sizeof(float);
+  if (sh > 160 * 1024) { set_error("peneo_pair_heads_fwd_mxfp8: D=%d, %d heads need %zu bytes of LDS", p.D, p.num_heads, sh); return PENEO_ERR_INVALID; }
+  if (sh > 64 * 1024 &&
+      hipFuncSetAttribute(reinterpret_cast<const void*>(pair_heads_mx_fwd_kernel<KS8, NSTAGE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh) != hipSuccess) {
+    set_error("peneo_pair_heads_fwd_mxfp8: cannot raise dynamic LDS to %zu bytes", sh);
+    return PENEO_ERR_LAUNCH;
+  }
+  dim3 grid((unsigned)((p.P + MX_PAIRS - 1) / MX_PAIRS), p.B);
+  hipLaunchKernelGGL((pair_heads_mx_fwd_kernel<KS8, NSTAGE>), grid, dim3(MX_WAVES * 64), sh, st, p);
+  return check_launch("peneo_pair_heads_fwd_mxfp8");
+}
+
+unsigned mx_blocks(int64_t n) {
+  const int64_t b = (n + 255) / 256;
+  return (unsigned)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
+}
+
+}  // namespace
+}  // namespace peneo
+
+using namespace peneo;
+
+extern "C" int peneo_mxfp8_quantize_rows(const float* src, int64_t rows, int64_t cols, void* q_e4m3, void* scales_e8m0,
+                                         peneo_stream_t stream) {
+  PENEO_REQUIRE(src && q_e4m3 && scales_e8m0 && rows > 0 && cols > 0, "peneo_mxfp8_quantize_rows: bad arguments");
+  PENEO_REQUIRE(cols % 32 == 0, "peneo_mxfp8_quantize_rows: cols must be a multiple of 32 (the MX block), got %lld", (long long)cols);
+  PENEO_REQUIRE((reinterpret_cast<uintptr_t>(src) & 15) == 0 && (reinterpret_cast<uintptr_t>(q_e4m3) & 15) == 0,
+                "peneo_mxfp8_quantize_rows: src / q must be 16-byte aligned");
+  const int64_t nblocks = rows * (cols / 32);
+  hipLaunchKernelGGL(mx_quantize_rows_kernel, dim3(mx_blocks(nblocks)), dim3(256), 0, (hipStream_t)stream, src, nblocks,
+                     static_cast<uint8_t*>(q_e4m3), static_cast<uint8_t*>(scales_e8m0));
+  return check_launch("peneo_mxfp8_quantize_rows");
+}
+
+extern "C" int peneo_pair_mxfp8_supported(int D, int num_heads) {
+  if (num_heads < 1 || num_heads > PENEO_MAX_HEADS || D < 64 || D > 64 * MX_MAX_KS || D % 64 != 0) return 0;
+  const int ks8 = D / 64;
+  const size_t sh = (size_t)mx_nstage(ks8) * mx_slab_bytes(ks8) + (size_t)num_heads * D * sizeof(float);
+  return sh <= 160 * 1024 ? 1 : 0;
+}
+
+extern "C" size_t peneo_pair_heads_mxfp8_packed_bytes(int num_heads, int D) {
+  if (!peneo_pair_mxfp8_supported(D, num_heads)) return 0;
+  return (size_t)(num_heads * D / 32) * (size_t)mx_slab_bytes(D / 64);
+}
+
+extern "C" int peneo_pair_heads_pack_mxfp8(const float* const* w1, const float* const* w2, const int* classes, int num_heads,
+                                           int D, void* packed, peneo_stream_t stream) {
+  PENEO_REQUIRE(w1 && w2 && classes && packed, "peneo_pair_heads_pack_mxfp8: bad arguments");
+  PENEO_REQUIRE(peneo_pair_mxfp8_supported(D, num_heads), "peneo_pair_heads_pack_mxfp8: D=%d with %d heads not supported (peneo_pair_mxfp8_supported)", D, num_heads);
+  PENEO_REQUIRE((reinterpret_cast<uintptr_t>(packed) & 15) == 0, "peneo_pair_heads_pack_mxfp8: packed must be 16-byte aligned");
+  MxPackSrc s = {};
+  s.num_heads = num_heads; s.D = D;
+  int tc = 0;
+  for (int h = 0; h < num_heads; ++h) {
+    PENEO_REQUIRE(w1[h] && w2[h], "peneo_pair_heads_pack_mxfp8: null weight pointer for head %d", h);
+    PENEO_REQUIRE(classes[h] >= 1 && classes[h] <= 4, "peneo_pair_heads_pack_mxfp8: classes[%d] must be 1..4", h);
+    s.w1[h] = w1[h]; s.w2[h] = w2[h]; s.classes[h] = classes[h]; tc += classes[h];
+  }
+  PENEO_REQUIRE(tc <= MX_NCP, "peneo_pair_heads_pack_mxfp8: more than %d classes in total", MX_NCP);
+  const hipStream_t st = (hipStream_t)stream;
+  if (hipMemsetAsync(packed, 0, peneo_pair_heads_mxfp8_packed_bytes(num_heads, D), st) != hipSuccess) {
+    set_error("peneo_pair_heads_pack_mxfp8: hipMemsetAsync failed");
+    return PENEO_ERR_LAUNCH;
+  }
+  hipLaunchKernelGGL(mx_pack_w1_kernel, dim3(mx_blocks((int64_t)num_heads * D * (D / 32))), dim3(256), 0, st, s, static_cast<char*>(packed));
+  hipLaunchKernelGGL(mx_pack_w2_kernel, dim3(mx_blocks((int64_t)(num_heads * D / 32) * 1024)), dim3(256), 0, st, s, static_cast<char*>(packed));
+  return check_launch("peneo_pair_heads_pack_mxfp8");
+}
+
+extern "C" int peneo_pair_heads_fwd_mxfp8(const void* ab, int B, int N, const peneo_pair_heads_desc* desc, float* const* logits,
+                                          const peneo_pair_loss* loss, peneo_stream_t stream) {
+  PENEO_REQUIRE(ab && desc && B > 0 && N > 0, "peneo_pair_heads_fwd_mxfp8: bad arguments");
+  PENEO_REQUIRE(peneo_pair_mxfp8_supported(desc->D, desc->num_heads), "peneo_pair_heads_fwd_mxfp8: D=%d with %d heads not supported (peneo_pair_mxfp8_supported)", desc->D, desc->num_heads);
+  PENEO_REQUIRE(desc->w_packed && desc->b1 && desc->b2, "peneo_pair_heads_fwd_mxfp8: null weights");
+  PENEO_REQUIRE((reinterpret_cast<uintptr_t>(desc->w_packed) & 15) == 0 && (reinterpret_cast<uintptr_t>(ab) & 15) == 0,
+                "peneo_pair_heads_fwd_mxfp8: ab / packed weights must be 16-byte aligned");
+  PENEO_REQUIRE(desc->drop_p == 0.f, "peneo_pair_heads_fwd_mxfp8: eval only, drop_p must be 0");
+  MxFwdParams p = {};
+  p.ab = static_cast<const bf16_t*>(ab); p.B = B; p.N = N; p.D = desc->D; p.P = (int64_t)N * (N + 1) / 2;
+  p.num_heads = desc->num_heads;
+  p.wp = static_cast<const char*>(desc->w_packed); p.b1 = desc->b1; p.b2 = desc->b2;
+  int tc = 0;
+  for (int h = 0; h < desc->num_heads; ++h) {
+    PENEO_REQUIRE(desc->classes[h] >= 1 && desc->classes[h] <= 4, "peneo_pair_heads_fwd_mxfp8: classes[%d] must be 1..4", h);
+    p.classes[h] = desc->classes[h]; tc += desc->classes[h];
+    p.logits[h] = logits ? logits[h] : nullptr;
+    if (loss) {
+      PENEO_REQUIRE(!loss->dlogits[h], "peneo_pair_heads_fwd_mxfp8: eval only, dlogits must be NULL");
+      p.tags[h] = loss->tags[h]; p.cw[h] = loss->class_weight[h];
+    }
+  }
+  PENEO_REQUIRE(tc <= MX_NCP, "peneo_pair_heads_fwd_mxfp8: more than %d classes in total", MX_NCP);
+  if (loss) {
+    p.partials = loss->partials;
+    bool any = false;
+    for (int h = 0; h < desc->num_heads; ++h) any = any || loss->tags[h];
+    if (any) PENEO_REQUIRE(p.partials, "peneo_pair_heads_fwd_mxfp8: loss->partials workspace missing");
+  }
+  const hipStream_t st = (hipStream_t)stream;
+  switch (desc->D / 64) {
+    case 1: return launch_mx_fwd<1>(p, st);
+    case 2: return launch_mx_fwd<2>(p, st);
+    case 3: return launch_mx_fwd<3>(p, st);
+    case 4: return launch_mx_fwd<4>(p, st);
+    case 5: return launch_mx_fwd<5>(p, st);
+    case 6: return launch_mx_fwd<6>(p, st);
+    case 7: return launch_mx_fwd<7>(p, st);
+    default: return launch_mx_fwd<8>(p, st);
+  }
+}

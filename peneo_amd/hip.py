@@ -152,6 +152,11 @@ SIGNATURES = {
     "peneo_pair_save_bytes": (_sz, [_i, _i, _i, _i]),
     "peneo_pair_loss_partials_save": (_i64, [_i, _i]),
     "peneo_pair_heads_fwd_save": (_i, [_i, _vp, _i, _i, C.POINTER(PairHeadsDesc), _vp, C.POINTER(PairLoss), _vp, _vp, _vp]),
+    "peneo_mxfp8_quantize_rows": (_i, [_vp, _i64, _i64, _vp, _vp, _vp]),
+    "peneo_pair_mxfp8_supported": (_i, [_i, _i]),
+    "peneo_pair_heads_mxfp8_packed_bytes": (_sz, [_i, _i]),
+    "peneo_pair_heads_pack_mxfp8": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "peneo_pair_heads_fwd_mxfp8": (_i, [_vp, _i, _i, C.POINTER(PairHeadsDesc), _vp, C.POINTER(PairLoss), _vp]),
     "peneo_pair_bwd_saved": (_i, [_i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "peneo_ohem_workspace_bytes": (_sz, [_i64]),
     "peneo_ohem_ce": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -175,10 +175,26 @@ class PEneoModel(PEneoPreTrainedModel):
         self.backbone.compute_dtype = dtype
         return self
 
+    def set_pair_heads_format(self, fmt: str) -> "PEneoModel":
+        """"bf16" (default) or "mxfp8": the MXFP8 inference path of the five pair classifiers (eval forwards without
+        gradients only; a forward with gradients raises ValueError).  "mxfp8" needs compute dtype torch.bfloat16, 2-layer
+        classifiers and a decoder width the kernel supports; otherwise this raises ValueError."""
+        if fmt == "mxfp8" and self._compute_dtype != torch.bfloat16:
+            raise ValueError("mxfp8 pair heads need set_compute_dtype(torch.bfloat16) first")
+        self.peneo_decoder.set_pair_heads_format(fmt)
+        return self
+
     def _init_weights(self, module) -> None:
         self.backbone._init_weights(module)
 
     def forward(self, input_ids, bbox, orig_bbox, attention_mask, image=None, **kwargs):
+        if self.peneo_decoder.pair_heads_format == "mxfp8":
+            # refused before anything runs: the MXFP8 pair heads have no backward, and they read bf16 activations
+            if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+                raise ValueError("mxfp8 pair heads are inference-only: run the forward under torch.no_grad() or switch back "
+                                 "with set_pair_heads_format('bf16')")
+            if self._compute_dtype != torch.bfloat16:
+                raise ValueError("mxfp8 pair heads need compute dtype torch.bfloat16")
         kwargs.update({"input_ids": input_ids, "bbox": bbox, "orig_bbox": orig_bbox, "attention_mask": attention_mask,
                        "image": image})
         reset_pending()   # joins left behind by a backward that raised (engine.py)

@@ -206,10 +206,18 @@ class _DecoderStage(torch.autograd.Function):
             return tuple(outs) + tuple(logits)
         w1s, b1s = [hd[0] for hd in heads], [hd[1] for hd in heads]
         w2s, b2s = [hd[2] for hd in heads], [hd[3] for hd in heads]
-        wp = wc.get(("dec.pack", dt), w1s + w2s, lambda: ops.pair_heads_pack(dt, [w.detach() for w in w1s],
-                                                                             [w.detach() for w in w2s]))
         b1cat = wc.get(("dec.b1",), b1s, lambda: torch.cat([b.detach() for b in b1s]))
         b2cat = wc.get(("dec.b2",), b2s, lambda: torch.cat([b.detach() for b in b2s]))
+        if dec.pair_heads_format == "mxfp8":
+            # eval-only MXFP8 first layer (PEneoDecoder.forward has refused a forward with gradients); its own pack and cache key
+            assert not need_grad
+            wpm = wc.get(("dec.pack_mxfp8",), w1s + w2s, lambda: ops.pair_heads_pack_mxfp8([w.detach() for w in w1s],
+                                                                                         [w.detach() for w in w2s]))
+            res = ops.pair_heads_fwd_mxfp8(ab, wpm, b1cat, b2cat, HEAD_CLASSES, want_logits=want_logits, tags=tags,
+                                           class_weights=cws)
+            return _DecoderStage._finish(ctx, dec, saved, params, res, tags, cws, ab, B, N, D, seq, dev)
+        wp = wc.get(("dec.pack", dt), w1s + w2s, lambda: ops.pair_heads_pack(dt, [w.detach() for w in w1s],
+                                                                             [w.detach() for w in w2s]))
         # the Dropout between the two layers of every classifier (reference :261) acts on the [B, P, 5D] hidden inside the
         # kernel; the backward regenerates the mask from (p, seed)
         saved["k12_drop"] = (seeds.p_hidden, seeds.seed(903))
@@ -237,6 +245,11 @@ class _DecoderStage(torch.autograd.Function):
         res = ops.pair_heads_fwd(ab, wp, b1cat, b2cat, HEAD_CLASSES, want_logits=want_logits,
                                  tags=tags, class_weights=cws, want_dlogits=need_grad and tags is not None,
                                  drop_p=seeds.p_hidden, drop_seed=seeds.seed(903), save=save, save_buffers=bufs)
+        return _DecoderStage._finish(ctx, dec, saved, params, res, tags, cws, ab, B, N, D, seq, dev)
+
+    @staticmethod
+    def _finish(ctx, dec, saved, params, res, tags, cws, ab, B, N, D, seq, dev):
+        """losses from the pair kernel's logits / partial rows (both formats) and the autograd bookkeeping"""
         logits, partials, dlog = res[:3]
         outs = []
         if tags is not None and dec.le_loss.ohem:
@@ -622,6 +635,7 @@ class PEneoDecoder(nn.Module):
         if D % 32 != 0:
             raise ValueError(f"decoder hidden size {D} must be a multiple of 32 for the MFMA pair-heads kernel")
         self.decoder_hidden_size = D
+        self.pair_heads_format = "bf16"   # set_pair_heads_format
         self.handshaking_kernel = HandshakingKernel(D)
         self.inference_mode = config.inference_mode
 
@@ -665,6 +679,19 @@ class PEneoDecoder(nn.Module):
         self.dw1_side_rows = 600_000     # ... none of them with more rows of K than this
         self.dw1_side_wgs = 144          # ... of about this many long workgroups (measured 18.10 ms per step against 18.56 at 495)
         self._ratio = {}
+
+    def set_pair_heads_format(self, fmt: str) -> None:
+        """"bf16" (default): the pair heads run in the compute dtype.  "mxfp8": eval forwards (no gradients) run the first
+        layer of the five classifiers on block-scaled e4m3 (include/peneo_hip.h, peneo_pair_heads_fwd_mxfp8); a forward with
+        gradients raises.  Needs the 2-layer classifiers and a decoder width the kernel holds."""
+        if fmt not in ("bf16", "mxfp8"):
+            raise ValueError(f"unknown pair-heads format {fmt!r} (expected 'bf16' or 'mxfp8')")
+        if fmt == "mxfp8":
+            if self.num_cls_layers != 2:
+                raise ValueError(f"mxfp8 pair heads need peneo_classifier_num_layers == 2, not {self.num_cls_layers}")
+            if not ops.pair_mxfp8_supported(self.decoder_hidden_size, len(HEAD_NAMES)):
+                raise ValueError(f"mxfp8 pair heads do not support decoder width D = {self.decoder_hidden_size}")
+        self.pair_heads_format = fmt
 
     def stacked_combine_weight(self, wc_w: torch.Tensor, dt: torch.dtype) -> torch.Tensor:
         """[Wc[:, :D]; Wc[:, D:]] as a [2D, D] working-precision matrix, so one GEMM yields [a | b]."""
@@ -727,6 +754,12 @@ class PEneoDecoder(nn.Module):
         # kernel's registers unless `train_logits` asks for them; eval / inference always returns them.
         want_logits = bool(self.train_logits) or not (self.training and need_grad and tags is not None) \
             or (tags is not None and self.le_loss.ohem)
+        if self.pair_heads_format == "mxfp8":
+            if need_grad:
+                raise ValueError("mxfp8 pair heads are inference-only: run the forward under torch.no_grad() or switch back "
+                                 "with set_pair_heads_format('bf16')")
+            if sequence_output.dtype != torch.bfloat16:
+                raise ValueError("mxfp8 pair heads need compute dtype torch.bfloat16")
         res = _DecoderStage.apply(self, sequence_output.reshape(B * N, Hin), B, N, tags, want_logits, need_grad, *params)
         loss, l_le, l_elh, l_elt, l_lgh, l_lgt, o_le, o_elh, o_elt, o_lgh, o_lgt = res
         if self.inference_mode:

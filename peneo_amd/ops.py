@@ -667,6 +667,71 @@ def pair_save_supported(dtype, D: int, num_heads: int) -> bool:
     return bool(lib().peneo_pair_save_supported(dtype_code(dtype), int(D), int(num_heads)))
 
 
+def mxfp8_quantize_rows(src: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """[rows, cols] fp32 (cols % 32 == 0) -> (e4m3 bytes [rows, cols] uint8, E8M0 bytes [rows, cols // 32] uint8): OCP MX
+    quantization with the rounding and clamping of the MXFP8 pair-heads path (include/peneo_hip.h)."""
+    src = _c(src)
+    assert src.dtype == torch.float32 and src.dim() == 2
+    rows, cols = src.shape
+    q = torch.empty((rows, cols), dtype=torch.uint8, device=src.device)
+    sc = torch.empty((rows, cols // 32), dtype=torch.uint8, device=src.device)
+    check(lib().peneo_mxfp8_quantize_rows(ptr(src), rows, cols, ptr(q), ptr(sc), stream()), "peneo_mxfp8_quantize_rows")
+    return q, sc
+
+
+def pair_mxfp8_supported(D: int, num_heads: int) -> bool:
+    """True when the MXFP8 pair-heads kernel holds this shape (host-side, no GPU call)."""
+    return bool(lib().peneo_pair_mxfp8_supported(int(D), int(num_heads)))
+
+
+def pair_heads_pack_mxfp8(w1: Sequence[torch.Tensor], w2: Sequence[torch.Tensor]) -> torch.Tensor:
+    """w1[h]: [D, D] fp32, w2[h]: [C_h, D] fp32 -> the packed buffer of pair_heads_fwd_mxfp8 (e4m3 + E8M0 first layer, bf16 second)."""
+    nh, D = len(w1), w1[0].shape[1]
+    nbytes = lib().peneo_pair_heads_mxfp8_packed_bytes(nh, D)
+    if nbytes == 0:
+        raise ValueError(f"MXFP8 pair heads: D={D} with {nh} heads is not supported")
+    packed = torch.empty(nbytes, dtype=torch.uint8, device=w1[0].device)
+    classes = (C.c_int * nh)(*[w.shape[0] for w in w2])
+    check(lib().peneo_pair_heads_pack_mxfp8(_ptr_list([_c(w) for w in w1]), _ptr_list([_c(w) for w in w2]), classes, nh, D,
+                                            ptr(packed), stream()), "peneo_pair_heads_pack_mxfp8")
+    return packed
+
+
+def pair_heads_fwd_mxfp8(ab: torch.Tensor, wp: torch.Tensor, b1: torch.Tensor, b2: torch.Tensor,
+                         classes: Sequence[int], *, want_logits: bool = True, tags: Optional[Sequence[torch.Tensor]] = None,
+                         class_weights: Optional[Sequence[Optional[torch.Tensor]]] = None):
+    """Eval-only MXFP8 form of pair_heads_fwd: ab [B, N, 2D] bf16, wp from pair_heads_pack_mxfp8.
+    Returns (logits list | None, loss partials [n, 32] | None, None) like pair_heads_fwd without dlogits."""
+    _c(ab)
+    assert ab.dtype == torch.bfloat16, "pair_heads_fwd_mxfp8 takes bf16 ab"
+    B, N, D2 = ab.shape
+    D = D2 // 2
+    P = N * (N + 1) // 2
+    nh = len(classes)
+    desc = hip.PairHeadsDesc()
+    desc.num_heads, desc.D = nh, D
+    for h, c in enumerate(classes):
+        desc.classes[h] = c
+    desc.w_packed, desc.b1, desc.b2 = ptr(wp), ptr(b1), ptr(b2)
+    desc.drop_p, desc.drop_seed = 0.0, 0
+    logits = [torch.empty((B, P, c), dtype=torch.float32, device=ab.device) for c in classes] if want_logits else None
+    lp = _ptr_list(logits) if logits is not None else None
+    loss = None
+    partials = None
+    if tags is not None:
+        loss = hip.PairLoss()
+        partials = torch.empty((lib().peneo_pair_loss_partials(B, N), 32), dtype=torch.float32, device=ab.device)
+        for h in range(nh):
+            assert tags[h].dtype == torch.int64 and tags[h].shape == (B, P)
+            loss.tags[h] = ptr(_c(tags[h]))
+            loss.class_weight[h] = ptr(class_weights[h]) if class_weights is not None else None
+        loss.partials = ptr(partials)
+    with kernel_timer("pair_heads_fwd_mxfp8"):
+        check(lib().peneo_pair_heads_fwd_mxfp8(ptr(ab), B, N, C.byref(desc), lp, C.byref(loss) if loss is not None else None,
+                                               stream()), "peneo_pair_heads_fwd_mxfp8")
+    return logits, partials, None
+
+
 def pair_x_fwd(ab_doc: torch.Tensor, i0: int, i1: int, out: torch.Tensor, pre: Optional[torch.Tensor] = None) -> torch.Tensor:
     """x = SiLU(a_i + b_j) for the pairs of rows i0..i1; `pre` (same shape) optionally receives a_i + b_j."""
     N, D2 = ab_doc.shape
