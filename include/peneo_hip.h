@@ -402,6 +402,37 @@ int peneo_pair_heads_fwd_mxfp8(const void* ab, int B, int N, const peneo_pair_he
                                float* const* logits /* host array of num_heads device pointers, or NULL */,
                                const peneo_pair_loss* loss, peneo_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Block-scaled (OCP MX v1.0) FP8 GEMM:  C[m, n] = epilogue( sum_k A^(m, k) * B^(n, k) ),  x^ = e4m3 element * 2^(E8M0 byte - 127)
+ * Both operands are k-major, as every forward nn.Linear (y = x W^T): A_q [M, K] e4m3 bytes with A_s [M, K / 32] E8M0 bytes, B_q [N, K]
+ * with B_s [N, K / 32], all contiguous, in the format peneo_mxfp8_quantize_rows writes (blocks of 32 consecutive k).  fp32 accumulation
+ * on v_mfma_scale_f32_32x32x64_f8f6f4; no split-k, no workspace, no allocation.  C [M, ldc] is bf16 or fp32 (`c_dtype`).
+ * Epilogue (`ep` may be NULL):  v = alpha * acc (+ bias[n]) ; v = act(v) (PENEO_ACT_NONE or PENEO_ACT_GELU; the erf form, evaluated as
+ * peneo_gemm does for the same c_dtype) ; v += residual[m, n] (dtype c_dtype) ; C <- v.  Any other field of `ep` being set (preact,
+ * grad_src, drop_p > 0, accumulate, pair_dz, a_colsum, another act) is PENEO_ERR_INVALID.
+ * MX output (C_q, C_s both non-NULL or both NULL): C_q [M, N] e4m3 and C_s [M, N / 32] E8M0 receive the quantization, along n, of the
+ * value AS ROUNDED TO bf16 -- byte for byte peneo_mxfp8_quantize_rows_bf16 of a bf16 C -- so that the next GEMM (FFN1 -> FFN2) reads
+ * it without a quantizer launch; C may then be NULL and is not written.
+ * Alignment: A_q, B_q, C, bias, residual 16 bytes; A_s, B_s, C_q 4 bytes; ldc and ld_res multiples of 4 and >= N.
+ * Rows of A past M and of B past N are neither read as data nor written.
+ * peneo_gemm_mxfp8_supported: host-side query (no GPU call): 1 when M >= 1 (ceil(M / 128) * ceil(N / 128) < 2^31), N >= 32 with N % 32 == 0 and
+ * K >= 128 with K % 128 == 0 (a K stage of the kernel is 128 deep and holds one dword of scales per row), else 0.
+ * peneo_mxfp8_quantize_rows_bf16: peneo_mxfp8_quantize_rows for a bf16 source [rows, ld] (ld >= cols, ld % 8 == 0, 16-byte aligned);
+ * q [rows, cols] and scales [rows, cols / 32] contiguous.  A bf16 value gives exactly the bytes its fp32 image gives there.
+ * ------------------------------------------------------------------------------------------ */
+int peneo_mxfp8_quantize_rows_bf16(const void* src, int64_t rows, int64_t cols, int64_t ld, void* q_e4m3, void* scales_e8m0,
+                                   peneo_stream_t stream);
+/* peneo_layernorm_fwd (bf16, contiguous [rows, H] x and y, no dropout) that also writes the MX copy of y: y, mean, rstd bit for bit those
+ * of peneo_layernorm_fwd, and y_q [rows, H] / y_s [rows, H / 32] byte for byte peneo_mxfp8_quantize_rows_bf16(y), in one launch.
+ * x, y, gamma, beta 16-byte aligned, y_q 8-byte aligned.  peneo_layernorm_mxfp8_supported (host-only): H % 256 == 0 and H <= 1024. */
+int peneo_layernorm_mxfp8_supported(int H);
+int peneo_layernorm_fwd_mxfp8(const void* x, void* y, const float* gamma, const float* beta, float eps, float* mean, float* rstd,
+                              int64_t rows, int H, void* y_q, void* y_s, peneo_stream_t stream);
+int peneo_gemm_mxfp8_supported(int M, int N, int K);
+int peneo_gemm_mxfp8(int M, int N, int K, const void* A_q, const void* A_s, const void* B_q, const void* B_s,
+                     void* C, int64_t ldc, int c_dtype, const peneo_gemm_epilogue* ep, void* C_q, void* C_s,
+                     peneo_stream_t stream);
+
 /* --- building blocks of the chunked backward (rows i0..i1 of the pair triangle = pairs
  *     p(i0,i0) .. p(i1,i1)-1 of one document) ------------------------------------------- */
 /* x[p - p0, :] = SiLU(a_i + b_j)  [npairs, D];  pre (may be NULL) receives a_i + b_j itself, the `grad_src` that lets the
@@ -576,13 +607,36 @@ typedef struct peneo_encoder_layer_grads {
   float* dwqkv; float* dbqkv; float* dwo; float* dbo; float* dg1; float* db1; float* dwi; float* dbi; float* dwo2; float* dbo2;
   float* dg2; float* db2;
 } peneo_encoder_layer_grads;
-/* sizeof of the structs shared with a binding: 0 peneo_gemm_epilogue, 1 peneo_encoder_layer, 2 peneo_encoder_layer_grads */
+/* sizeof of the structs shared with a binding: 0 peneo_gemm_epilogue, 1 peneo_encoder_layer, 2 peneo_encoder_layer_grads,
+ * 3 peneo_encoder_layer_mxfp8 */
 size_t peneo_struct_bytes(int which);
 /* workspace of the layer's GEMMs (as peneo_gemm_workspace_bytes): which = 0 forward, 1 backward main stream (dgrads), 2 backward
  * side stream (wgrads) */
 size_t peneo_encoder_layer_workspace_bytes(int rows, int H, int I, int which);
 int peneo_encoder_layer_fwd(const peneo_encoder_layer* layer, void* out, void* workspace, size_t workspace_bytes,
                             peneo_stream_t stream);
+/* MXFP8 inference form of peneo_encoder_layer_fwd (no backward): the four nn.Linear products run on peneo_gemm_mxfp8, attention and
+ * the two LayerNorms stay bf16.  `layer` as above, except that Wqkv / Wo / Wi / Wo2, inter and zi are not used (zi must be NULL) and
+ * p_hidden == p_attn == 0; `mx` carries the weights quantized with peneo_mxfp8_quantize_rows (W*_q [out, in] e4m3, W*_s [out, in / 32]
+ * E8M0) and the caller's MX scratch: x_q / att_q / a_q [rows, H], inter_q [rows, I], each with its scales [rows, cols / 32].  Every
+ * shape must pass peneo_gemm_mxfp8_supported: (rows, 3H, H), (rows, H, H), (rows, I, H), (rows, H, I).  The call is the composition
+ * of the public entry points, in this order: quantize x; QKV product + bias; peneo_attn_fwd; quantize att; output projection + bias +
+ * residual x -> h1; peneo_layernorm_fwd -> a; quantize a; FFN1 + bias + GELU -> inter_q / inter_s only (the bf16 `inter` is not
+ * written); FFN2 + bias + residual a -> h2; peneo_layernorm_fwd -> out.  Where peneo_layernorm_mxfp8_supported(H), "LayerNorm, then
+ * quantize" is the single call peneo_layernorm_fwd_mxfp8 (the same bytes).  No workspace.
+ * Chaining layers: with out_q / out_s non-NULL the last LayerNorm also leaves the MX copy of `out` there ([rows, H], [rows, H / 32]:
+ * byte for byte the quantization of `out`); with x_prequantized != 0 the call takes x_q / x_s as the valid MX copy of x (the out_q /
+ * out_s of the layer before) and skips its first quantizer. */
+typedef struct peneo_encoder_layer_mxfp8 {
+  const void* Wqkv_q; const void* Wqkv_s; const void* Wo_q; const void* Wo_s;
+  const void* Wi_q; const void* Wi_s; const void* Wo2_q; const void* Wo2_s;
+  void* x_q; void* x_s; void* att_q; void* att_s; void* a_q; void* a_s; void* inter_q; void* inter_s;
+  void* out_q; void* out_s;          /* optional, both or neither */
+  int32_t x_prequantized, reserved;
+} peneo_encoder_layer_mxfp8;
+int peneo_encoder_layer_mxfp8_supported(int rows, int H, int I);
+int peneo_encoder_layer_fwd_mxfp8(const peneo_encoder_layer* layer, const peneo_encoder_layer_mxfp8* mx, void* out,
+                                  peneo_stream_t stream);
 /* The activation-gradient chain runs on `stream`; the parameter-gradient work (weight-gradient GEMMs, bias column sums) on
  * `side_stream` behind HIP events recorded on `stream` (the FFN / output-projection part starts with the attention backward,
  * the QKV part behind it).  The call does NOT join the two streams: the caller waits for `side_stream` before anything

@@ -22,6 +22,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "mx_common.h"
 
 namespace peneo {
 namespace {
@@ -31,7 +32,6 @@ constexpr int MX_PAIRS = MX_WAVES * 32;   // as PH_PAIRS: the loss partial rows 
 constexpr int MX_NCP = 16;
 constexpr int MX_MAX_KS = 8;              // D <= 512 (x: D / 8 VGPRs per lane)
 constexpr float NEG_INF_MX = -3.0e38f;
-typedef int i32x8_t __attribute__((ext_vector_type(8)));
 
 // Packed slab (32 hidden rows of W1cat, 16-byte aligned parts):
 //   KS8 = D / 64 first-layer fragments of 2 KiB: byte (c * 1024 + lane * 16 + t) of fragment ks =
@@ -47,39 +47,16 @@ __host__ __device__ constexpr int mx_slab_bytes(int ks8) { return mx_upw(ks8) * 
 // ring depth: 3 while two workgroups still fit a CU's 160 KiB of LDS, else 2
 __host__ __device__ constexpr int mx_nstage(int ks8) { return ks8 <= 6 ? 3 : 2; }
 
-// E8M0 byte of a block with maximum magnitude amax (>= 0): max(floor(log2 amax) - 8, -127) + 127, read off the exponent field
-__device__ __forceinline__ uint32_t mx_scale_byte(float amax) {
-  const int e = (int)((__float_as_uint(amax) >> 23) & 255u) - 8;
-  return (uint32_t)(e < 0 ? 0 : e);
-}
-// 1 / 2^(byte - 127), exact (byte <= 247)
-__device__ __forceinline__ float mx_inv_scale(uint32_t byte) { return __uint_as_float((254u - byte) << 23); }
-// four values (already divided by the block scale) -> four e4m3 bytes, little-endian in order
-__device__ __forceinline__ uint32_t mx_e4m3x4(float v0, float v1, float v2, float v3) {
-  v0 = fminf(fmaxf(v0, -448.f), 448.f); v1 = fminf(fmaxf(v1, -448.f), 448.f);
-  v2 = fminf(fmaxf(v2, -448.f), 448.f); v3 = fminf(fmaxf(v3, -448.f), 448.f);
-  int w = __builtin_amdgcn_cvt_pk_fp8_f32(v0, v1, 0, false);
-  w = __builtin_amdgcn_cvt_pk_fp8_f32(v2, v3, w, true);
-  return (uint32_t)w;
-}
-// one block of 32 values -> 8 dwords of e4m3 + its E8M0 byte
-__device__ __forceinline__ uint32_t mx_quantize32(const float (&v)[32], uint32_t (&q)[8]) {
-  float amax = 0.f;
-#pragma unroll
-  for (int t = 0; t < 32; ++t) amax = fmaxf(amax, fabsf(v[t]));
-  const uint32_t sb = mx_scale_byte(amax);
-  const float inv = mx_inv_scale(sb);
-#pragma unroll
-  for (int w = 0; w < 8; ++w) q[w] = mx_e4m3x4(v[4 * w] * inv, v[4 * w + 1] * inv, v[4 * w + 2] * inv, v[4 * w + 3] * inv);
-  return sb;
-}
-
-__global__ __launch_bounds__(256) void mx_quantize_rows_kernel(const float* src, int64_t nblocks, uint8_t* q, uint8_t* sc) {
+// one thread per block of 32 elements of a row-major [rows, ld] source (fp32 or bf16: a bf16 value and its fp32 image quantize alike)
+template <typename T>
+__global__ __launch_bounds__(256) void mx_quantize_rows_kernel(const T* src, int64_t nblocks, int bpr, int64_t ld, uint8_t* q, uint8_t* sc) {
   for (int64_t blk = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; blk < nblocks; blk += (int64_t)gridDim.x * blockDim.x) {
     float v[32];
-    const float4* s4 = reinterpret_cast<const float4*>(src + blk * 32);
+    const int64_t row = blk / bpr;
+    const uint4* s4 = reinterpret_cast<const uint4*>(src + row * ld + (blk - row * bpr) * 32);
+    constexpr int VEC = Elem<T>::kVec;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) { const float4 f = s4[i]; v[4 * i] = f.x; v[4 * i + 1] = f.y; v[4 * i + 2] = f.z; v[4 * i + 3] = f.w; }
+    for (int i = 0; i < 32 / VEC; ++i) unpack16<T>(s4[i], v + VEC * i);
     uint32_t w[8];
     sc[blk] = (uint8_t)mx_quantize32(v, w);
     uint4* d4 = reinterpret_cast<uint4*>(q + blk * 32);
@@ -386,9 +363,23 @@ extern "C" int peneo_mxfp8_quantize_rows(const float* src, int64_t rows, int64_t
   PENEO_REQUIRE((reinterpret_cast<uintptr_t>(src) & 15) == 0 && (reinterpret_cast<uintptr_t>(q_e4m3) & 15) == 0,
                 "peneo_mxfp8_quantize_rows: src / q must be 16-byte aligned");
   const int64_t nblocks = rows * (cols / 32);
-  hipLaunchKernelGGL(mx_quantize_rows_kernel, dim3(mx_blocks(nblocks)), dim3(256), 0, (hipStream_t)stream, src, nblocks,
-                     static_cast<uint8_t*>(q_e4m3), static_cast<uint8_t*>(scales_e8m0));
+  hipLaunchKernelGGL(mx_quantize_rows_kernel<float>, dim3(mx_blocks(nblocks)), dim3(256), 0, (hipStream_t)stream, src, nblocks,
+                     (int)(cols / 32), cols, static_cast<uint8_t*>(q_e4m3), static_cast<uint8_t*>(scales_e8m0));
   return check_launch("peneo_mxfp8_quantize_rows");
+}
+
+extern "C" int peneo_mxfp8_quantize_rows_bf16(const void* src, int64_t rows, int64_t cols, int64_t ld, void* q_e4m3, void* scales_e8m0,
+                                              peneo_stream_t stream) {
+  PENEO_REQUIRE(src && q_e4m3 && scales_e8m0 && rows > 0 && cols > 0, "peneo_mxfp8_quantize_rows_bf16: bad arguments");
+  PENEO_REQUIRE(cols % 32 == 0 && cols <= (int64_t)32 * 0x7fffffff, "peneo_mxfp8_quantize_rows_bf16: cols must be a multiple of 32 (the MX block), got %lld", (long long)cols);
+  PENEO_REQUIRE(ld >= cols && ld % 8 == 0, "peneo_mxfp8_quantize_rows_bf16: ld must be >= cols and a multiple of 8, got %lld", (long long)ld);
+  PENEO_REQUIRE((reinterpret_cast<uintptr_t>(src) & 15) == 0 && (reinterpret_cast<uintptr_t>(q_e4m3) & 15) == 0,
+                "peneo_mxfp8_quantize_rows_bf16: src / q must be 16-byte aligned");
+  const int64_t nblocks = rows * (cols / 32);
+  hipLaunchKernelGGL(mx_quantize_rows_kernel<bf16_t>, dim3(mx_blocks(nblocks)), dim3(256), 0, (hipStream_t)stream,
+                     static_cast<const bf16_t*>(src), nblocks, (int)(cols / 32), ld, static_cast<uint8_t*>(q_e4m3),
+                     static_cast<uint8_t*>(scales_e8m0));
+  return check_launch("peneo_mxfp8_quantize_rows_bf16");
 }
 
 extern "C" int peneo_pair_mxfp8_supported(int D, int num_heads) {

@@ -74,7 +74,8 @@ bool layer_ok(const peneo_encoder_layer* L) {
 }  // namespace
 
 extern "C" size_t peneo_struct_bytes(int which) {
-  return which == 0 ? sizeof(peneo_gemm_epilogue) : which == 1 ? sizeof(peneo_encoder_layer) : which == 2 ? sizeof(peneo_encoder_layer_grads) : 0;
+  return which == 0 ? sizeof(peneo_gemm_epilogue) : which == 1 ? sizeof(peneo_encoder_layer) : which == 2 ? sizeof(peneo_encoder_layer_grads) :
+         which == 3 ? sizeof(peneo_encoder_layer_mxfp8) : 0;
 }
 
 extern "C" size_t peneo_encoder_layer_workspace_bytes(int rows, int H, int I, int which) {
@@ -113,6 +114,64 @@ extern "C" int peneo_encoder_layer_fwd(const peneo_encoder_layer* L, void* out, 
   ep.bias = L->bo2; ep.residual = L->a; ep.ld_res = H; ep.drop_p = L->p_hidden; ep.drop_seed = L->seed_o2;
   STAGE_TRY(gemm(1, 1, R, H, I, L->inter, I, L->Wo2, I, L->h2, H, PENEO_BF16, ep, ws, st));
   STAGE_TRY(peneo_layernorm_fwd(PENEO_BF16, L->h2, 0, 0, out, 0, 0, L->g2, L->b2, L->eps, L->m2, L->r2, R, H, 0.f, 0u, st));
+  return PENEO_OK;
+}
+
+extern "C" int peneo_encoder_layer_mxfp8_supported(int rows, int H, int I) {
+  return rows > 0 && H > 0 && I > 0 && H <= 0x7fffffff / 3 && peneo_gemm_mxfp8_supported(rows, 3 * H, H) && peneo_gemm_mxfp8_supported(rows, H, H) &&
+         peneo_gemm_mxfp8_supported(rows, I, H) && peneo_gemm_mxfp8_supported(rows, H, I);
+}
+
+// MXFP8 inference forward: the same chain with the four products on peneo_gemm_mxfp8 (gemm_mx.hip) and a row quantizer in front of
+// each operand that does not come out of a GEMM epilogue; FFN1 hands its output to FFN2 as MX bytes only.
+extern "C" int peneo_encoder_layer_fwd_mxfp8(const peneo_encoder_layer* L, const peneo_encoder_layer_mxfp8* X, void* out,
+                                             peneo_stream_t stream) {
+  PENEO_REQUIRE(L && X && out && L->B > 0 && L->T > 0 && L->H > 0 && L->nh > 0 && L->I > 0 && L->H % L->nh == 0,
+                "peneo_encoder_layer_fwd_mxfp8: incomplete layer description");
+  PENEO_REQUIRE(L->bqkv && L->bo && L->g1 && L->b1 && L->bi && L->bo2 && L->g2 && L->b2 && L->x && L->qkv && L->att && L->lse && L->h1 &&
+                    L->m1 && L->r1 && L->a && L->h2 && L->m2 && L->r2,
+                "peneo_encoder_layer_fwd_mxfp8: incomplete layer description");
+  PENEO_REQUIRE(X->Wqkv_q && X->Wqkv_s && X->Wo_q && X->Wo_s && X->Wi_q && X->Wi_s && X->Wo2_q && X->Wo2_s && X->x_q && X->x_s && X->att_q &&
+                    X->att_s && X->a_q && X->a_s && X->inter_q && X->inter_s,
+                "peneo_encoder_layer_fwd_mxfp8: incomplete MX description");
+  PENEO_REQUIRE((X->out_q == nullptr) == (X->out_s == nullptr), "peneo_encoder_layer_fwd_mxfp8: out_q and out_s go together");
+  PENEO_REQUIRE(L->p_hidden == 0.f && L->p_attn == 0.f, "peneo_encoder_layer_fwd_mxfp8: inference only, dropout must be off");
+  PENEO_REQUIRE(L->zi == nullptr, "peneo_encoder_layer_fwd_mxfp8: inference only, zi (the GELU pre-activation a backward needs) must be NULL");
+  PENEO_REQUIRE((int64_t)L->B * L->T <= 0x7fffffff && peneo_encoder_layer_mxfp8_supported(L->B * L->T, L->H, L->I),
+                "peneo_encoder_layer_fwd_mxfp8: rows=%lld H=%d I=%d not supported (peneo_encoder_layer_mxfp8_supported)",
+                (long long)L->B * L->T, L->H, L->I);
+  hipStream_t st = (hipStream_t)stream;
+  const int R = L->B * L->T, H = L->H, I = L->I, d = H / L->nh;
+  const char* qkv = reinterpret_cast<const char*>(L->qkv);
+  peneo_gemm_epilogue ep = {};
+  // LayerNorm + quantizer: one launch where the fused kernel holds H (the same bytes either way)
+  const bool ln_mx = peneo_layernorm_mxfp8_supported(H) != 0;
+  auto ln_then_quantize = [&](const void* h, void* y, const float* g, const float* b, float* m, float* r, void* yq, void* ys) -> int {
+    if (ln_mx) return peneo_layernorm_fwd_mxfp8(h, y, g, b, L->eps, m, r, R, H, yq, ys, st);
+    STAGE_TRY(peneo_layernorm_fwd(PENEO_BF16, h, 0, 0, y, 0, 0, g, b, L->eps, m, r, R, H, 0.f, 0u, st));
+    return peneo_mxfp8_quantize_rows_bf16(y, R, H, H, yq, ys, st);
+  };
+  if (!X->x_prequantized) STAGE_TRY(peneo_mxfp8_quantize_rows_bf16(L->x, R, H, H, X->x_q, X->x_s, st));
+  ep.bias = L->bqkv;
+  STAGE_TRY(peneo_gemm_mxfp8(R, 3 * H, H, X->x_q, X->x_s, X->Wqkv_q, X->Wqkv_s, L->qkv, 3 * H, PENEO_BF16, &ep, nullptr, nullptr, st));
+  STAGE_TRY(peneo_attn_fwd(PENEO_BF16, qkv, qkv + 2 * (size_t)H, qkv + 4 * (size_t)H, 3 * H, nullptr, L->B, L->nh, L->T, d, L->attn_scale,
+                           L->bias, L->bias_ld, L->key_bias, L->att, H, L->lse, 0.f, nullptr, st));
+  STAGE_TRY(peneo_mxfp8_quantize_rows_bf16(L->att, R, H, H, X->att_q, X->att_s, st));
+  ep = {};
+  ep.bias = L->bo; ep.residual = L->x; ep.ld_res = H;
+  STAGE_TRY(peneo_gemm_mxfp8(R, H, H, X->att_q, X->att_s, X->Wo_q, X->Wo_s, L->h1, H, PENEO_BF16, &ep, nullptr, nullptr, st));
+  STAGE_TRY(ln_then_quantize(L->h1, L->a, L->g1, L->b1, L->m1, L->r1, X->a_q, X->a_s));
+  ep = {};
+  ep.bias = L->bi; ep.act = PENEO_ACT_GELU;
+  STAGE_TRY(peneo_gemm_mxfp8(R, I, H, X->a_q, X->a_s, X->Wi_q, X->Wi_s, nullptr, I, PENEO_BF16, &ep, X->inter_q, X->inter_s, st));
+  ep = {};
+  ep.bias = L->bo2; ep.residual = L->a; ep.ld_res = H;
+  STAGE_TRY(peneo_gemm_mxfp8(R, H, I, X->inter_q, X->inter_s, X->Wo2_q, X->Wo2_s, L->h2, H, PENEO_BF16, &ep, nullptr, nullptr, st));
+  if (X->out_q) {
+    STAGE_TRY(ln_then_quantize(L->h2, out, L->g2, L->b2, L->m2, L->r2, X->out_q, X->out_s));
+  } else {
+    STAGE_TRY(peneo_layernorm_fwd(PENEO_BF16, L->h2, 0, 0, out, 0, 0, L->g2, L->b2, L->eps, L->m2, L->r2, R, H, 0.f, 0u, st));
+  }
   return PENEO_OK;
 }
 

@@ -44,6 +44,12 @@ class EncoderLayer(C.Structure):
                 [(n, _f) for n in ("eps", "attn_scale", "p_hidden", "p_attn")] + [("seed_o", _u32), ("seed_o2", _u32)])
 
 
+class EncoderLayerMxfp8(C.Structure):
+    _fields_ = [(n, _vp) for n in ("Wqkv_q", "Wqkv_s", "Wo_q", "Wo_s", "Wi_q", "Wi_s", "Wo2_q", "Wo2_s",
+                                   "x_q", "x_s", "att_q", "att_s", "a_q", "a_s", "inter_q", "inter_s", "out_q", "out_s")] + \
+               [("x_prequantized", _i), ("reserved", _i)]
+
+
 class EncoderLayerGrads(C.Structure):
     _fields_ = [(n, _vp) for n in ("d_out", "d_x", "d_h2", "d_dense2", "d_zi", "d_a", "d_h1", "d_dense1", "d_att", "dqkv", "delta",
                                    "ds_out", "dwqkv", "dbqkv", "dwo", "dbo", "dg1", "db1", "dwi", "dbi", "dwo2", "dbo2", "dg2", "db2")]
@@ -153,6 +159,11 @@ SIGNATURES = {
     "peneo_pair_loss_partials_save": (_i64, [_i, _i]),
     "peneo_pair_heads_fwd_save": (_i, [_i, _vp, _i, _i, C.POINTER(PairHeadsDesc), _vp, C.POINTER(PairLoss), _vp, _vp, _vp]),
     "peneo_mxfp8_quantize_rows": (_i, [_vp, _i64, _i64, _vp, _vp, _vp]),
+    "peneo_mxfp8_quantize_rows_bf16": (_i, [_vp, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "peneo_layernorm_mxfp8_supported": (_i, [_i]),
+    "peneo_layernorm_fwd_mxfp8": (_i, [_vp, _vp, _vp, _vp, _f, _vp, _vp, _i64, _i, _vp, _vp, _vp]),
+    "peneo_gemm_mxfp8_supported": (_i, [_i, _i, _i]),
+    "peneo_gemm_mxfp8": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i64, _i, _vp, _vp, _vp, _vp]),
     "peneo_pair_mxfp8_supported": (_i, [_i, _i]),
     "peneo_pair_heads_mxfp8_packed_bytes": (_sz, [_i, _i]),
     "peneo_pair_heads_pack_mxfp8": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
@@ -169,6 +180,8 @@ SIGNATURES = {
     "peneo_struct_bytes": (C.c_size_t, [_i]),
     "peneo_encoder_layer_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i]),
     "peneo_encoder_layer_fwd": (_i, [_vp, _vp, _vp, C.c_size_t, _vp]),
+    "peneo_encoder_layer_mxfp8_supported": (_i, [_i, _i, _i]),
+    "peneo_encoder_layer_fwd_mxfp8": (_i, [_vp, _vp, _vp, _vp]),
     "peneo_encoder_layer_bwd": (_i, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp]),
     "peneo_spots_to_tags": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
     "peneo_spots_compact": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp, _i, _vp]),

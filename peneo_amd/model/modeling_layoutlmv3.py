@@ -22,7 +22,7 @@ import torch.nn as nn
 import ctypes as C
 
 from .. import ops
-from ..hip import ACT_GELU, ACT_NONE, EncoderLayer, EncoderLayerGrads, PeneoHipError, check, ptr
+from ..hip import ACT_GELU, ACT_NONE, EncoderLayer, EncoderLayerGrads, EncoderLayerMxfp8, PeneoHipError, check, ptr
 from ..hip import lib as hip_lib
 from ..hip import stream as hip_stream
 from .configuration_peneo import LayoutLMv3Config
@@ -462,6 +462,92 @@ def _stage_backward(ctx, d_out):
     return (None, None, None, d_x) + grads
 
 # ------------------------------------------------------------------------------------------------
+# MXFP8 inference form of a layer (set_encoder_format("mxfp8")): ONE C call, peneo_encoder_layer_fwd_mxfp8.  No autograd node:
+# the path has no backward and only runs without gradients.
+# ------------------------------------------------------------------------------------------------
+class _MxScratch:
+    """Per-forward buffers shared by all layers: the bf16 activations of a layer, its statistics and the MX copies of the four
+    GEMM inputs (x, att, a [R, H], inter [R, I]; e4m3 bytes + E8M0 scales)."""
+    __slots__ = ("flat", "stats", "mx", "R", "H", "I", "o")
+
+    def __init__(self, R: int, H: int, I: int, nlse: int, dev) -> None:
+        self.R, self.H, self.I, self.o = R, H, I, nlse
+        self.flat = torch.empty(R * 7 * H, dtype=torch.bfloat16, device=dev)               # qkv | att | h1 | a | h2
+        self.stats = torch.empty(nlse + 4 * R, dtype=torch.float32, device=dev)            # lse | m1 | r1 | m2 | r2
+        self.mx = torch.empty(R * (4 * H + I) + R * (4 * H + I) // 32, dtype=torch.uint8, device=dev)
+
+    def fill(self, L, X, idx: int, last: bool) -> None:
+        R, H, I = self.R, self.H, self.I
+        b = self.flat.data_ptr()
+        L.qkv = b
+        L.att = b + 2 * R * 3 * H
+        L.h1 = L.att + 2 * R * H
+        L.a = L.h1 + 2 * R * H
+        L.h2 = L.a + 2 * R * H
+        L.inter, L.zi = None, None
+        s = self.stats.data_ptr()
+        L.lse = s
+        L.m1 = s + 4 * self.o
+        L.r1 = L.m1 + 4 * R
+        L.m2 = L.r1 + 4 * R
+        L.r2 = L.m2 + 4 * R
+        m = self.mx.data_ptr()                      # (R * H and R * H / 32 keep every part 4-byte aligned: H % 128 == 0)
+        X.att_q, X.a_q, X.inter_q = m + 2 * R * H, m + 3 * R * H, m + 4 * R * H
+        sc = m + R * (4 * H + I)
+        X.att_s, X.a_s, X.inter_s = sc + 2 * R * H // 32, sc + 3 * R * H // 32, sc + 4 * R * H // 32
+        # the MX copy of a layer's input is left behind by the layer before it (its last LayerNorm): two buffers, taken in turn
+        cur, nxt = idx & 1, (idx + 1) & 1
+        X.x_q, X.x_s = m + cur * R * H, sc + cur * R * H // 32
+        X.x_prequantized = 1 if idx > 0 else 0
+        if not last:
+            X.out_q, X.out_s = m + nxt * R * H, sc + nxt * R * H // 32
+
+
+def _mx_weights(model, idx, params):
+    """(q, scales) of Wqkv, Wo, Wi, Wo2 of layer idx: quantized once per weight version from the fp32 masters."""
+    (wq, _, wk, _, wv, _, wo, _, _, _, wi, _, wo2, _, _, _) = params
+    wc = model.weight_cache
+    quant = lambda ps: ops.mxfp8_quantize_rows(torch.cat([p.detach().float() for p in ps]) if len(ps) > 1 else ps[0].detach().float())
+    return (wc.get((f"L{idx}.qkv", "mxfp8"), [wq, wk, wv], lambda: quant([wq, wk, wv])),
+            wc.get((f"L{idx}.o", "mxfp8"), [wo], lambda: quant([wo])),
+            wc.get((f"L{idx}.i", "mxfp8"), [wi], lambda: quant([wi])),
+            wc.get((f"L{idx}.o2", "mxfp8"), [wo2], lambda: quant([wo2])))
+
+
+def _mx_layer_forward(model, st, idx, x, params):
+    (wq, bq, wk, bk, wv, bv, wo, bo, g1, b1, wi, bi, wo2, bo2, g2, b2) = params
+    cfg, wc = model.config, model.weight_cache
+    B, S, T = st.dims
+    H, nh, I = cfg.hidden_size, cfg.num_attention_heads, cfg.intermediate_size
+    R, dev = B * T, x.device
+    if not x.is_contiguous():
+        x = x.contiguous()
+    if getattr(st, "mx_scratch", None) is None:
+        if not ops.encoder_layer_mxfp8_supported(R, H, I):
+            raise ValueError(f"mxfp8 encoder: rows = {R}, H = {H}, I = {I} is not supported by peneo_gemm_mxfp8")
+        st.mx_scratch = _MxScratch(R, H, I, B * nh * T, dev)
+    (Wqkv, Sqkv), (Wo, So), (Wi, Si), (Wo2, So2) = weights = _mx_weights(model, idx, params)
+    bqkv = wc.get((f"L{idx}.bqkv",), [bq, bk, bv], lambda: torch.cat([bq.detach(), bk.detach(), bv.detach()]))
+    L, X = EncoderLayer(), EncoderLayerMxfp8()
+    X.Wqkv_q, X.Wqkv_s, X.Wo_q, X.Wo_s = Wqkv.data_ptr(), Sqkv.data_ptr(), Wo.data_ptr(), So.data_ptr()
+    X.Wi_q, X.Wi_s, X.Wo2_q, X.Wo2_s = Wi.data_ptr(), Si.data_ptr(), Wo2.data_ptr(), So2.data_ptr()
+    L.bqkv, L.bo, L.g1, L.b1 = bqkv.data_ptr(), bo.data_ptr(), g1.data_ptr(), b1.data_ptr()
+    L.bi, L.bo2, L.g2, L.b2 = bi.data_ptr(), bo2.data_ptr(), g2.data_ptr(), b2.data_ptr()
+    if st.bias is not None:
+        L.bias, L.bias_ld = st.bias.data_ptr(), st.bias.shape[-1]
+    if st.key_bias is not None:
+        L.key_bias = st.key_bias.data_ptr()
+    L.x = x.data_ptr()
+    st.mx_scratch.fill(L, X, idx, idx == cfg.num_hidden_layers - 1)
+    L.B, L.T, L.H, L.nh, L.I = B, T, H, nh, I
+    L.eps, L.attn_scale, L.p_hidden, L.p_attn = cfg.layer_norm_eps, 1.0 / math.sqrt(H // nh), 0.0, 0.0
+    out = torch.empty((R, H), dtype=torch.bfloat16, device=dev)
+    ops.encoder_layer_fwd_mxfp8(L, X, out)
+    del weights, bqkv        # (cached: they outlive the call)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
 # stage 2: one encoder layer
 # ------------------------------------------------------------------------------------------------
 class _LayerStage(torch.autograd.Function):
@@ -642,9 +728,39 @@ class LayoutLMv3Model(nn.Module):
             self.norm = nn.LayerNorm(H, eps=1e-6)
         self.weight_cache = WeightCache()
         self.compute_dtype = torch.float32
+        self.encoder_format = "bf16"      # set_encoder_format
         self.wgrad_on_side_stream = os.environ.get("PENEO_WGRAD_STREAM", "1") != "0"
         self.defer_wgrad_join = os.environ.get("PENEO_DEFER_JOIN", "1") != "0"
         self._luts = {}
+
+    # ---- precision of the encoder layers' four nn.Linear products ------------------------------
+    def set_encoder_format(self, fmt: str) -> "LayoutLMv3Model":
+        """"bf16" (default): the layers run in the compute dtype.  "mxfp8": eval forwards without gradients run every encoder layer
+        through peneo_encoder_layer_fwd_mxfp8 (QKV, output projection, FFN1, FFN2 on block-scaled e4m3 with weights quantized once
+        per weight version from the fp32 masters; attention, LayerNorm, embeddings and the patch embedding stay bf16).  Needs compute
+        dtype torch.bfloat16 and layer shapes peneo_gemm_mxfp8 supports, else ValueError; a forward with gradients raises ValueError."""
+        if fmt not in ("bf16", "mxfp8"):
+            raise ValueError(f"unknown encoder format {fmt!r} (expected 'bf16' or 'mxfp8')")
+        if fmt == "mxfp8":
+            if self.compute_dtype != torch.bfloat16:
+                raise ValueError("mxfp8 encoder layers need compute dtype torch.bfloat16")
+            H, I = self.config.hidden_size, self.config.intermediate_size
+            if not ops.encoder_layer_mxfp8_supported(1, H, I):
+                raise ValueError(f"mxfp8 encoder layers do not support H = {H}, I = {I} (peneo_gemm_mxfp8 needs K % 128 == 0, N % 32 == 0)")
+        self.encoder_format = fmt
+        return self
+
+    def check_encoder_format(self) -> None:
+        """Raises before anything runs when the MXFP8 encoder cannot serve this forward (it has no backward and reads bf16)."""
+        if self.encoder_format != "mxfp8":
+            return
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise ValueError("mxfp8 encoder layers are inference-only: run the forward under torch.no_grad() or switch back "
+                             "with set_encoder_format('bf16')")
+        if self.compute_dtype != torch.bfloat16:
+            raise ValueError("mxfp8 encoder layers need compute dtype torch.bfloat16")
+        if self.training and (self.config.hidden_dropout_prob > 0 or self.config.attention_probs_dropout_prob > 0):
+            raise ValueError("mxfp8 encoder layers have no dropout: call .eval() first")
 
     # ---- small host-side constants ---------------------------------------------------------
     def lut(self, kind: str, bins: int, max_dist: int, dev) -> torch.Tensor:
@@ -777,6 +893,7 @@ class LayoutLMv3Model(nn.Module):
         if not input_ids.is_cuda:
             raise PeneoHipError("peneo_amd runs on the GPU only: move the model and the batch to 'cuda' "
                                 "(there is no CPU fallback; the CPU oracle lives in oracle/ for tests)")
+        self.check_encoder_format()
         cfg = self.config
         B, S = input_ids.shape
         if bbox is None:
@@ -794,8 +911,9 @@ class LayoutLMv3Model(nn.Module):
                               attention_mask.contiguous() if attention_mask is not None else None, image,
                               *self.embed_params())
         _, _, T = st.dims
+        mx = self.encoder_format == "mxfp8"
         for i, layer in enumerate(self.encoder.layer):
-            x = _LayerStage.apply(self, st, i, x, *layer_params(layer))
+            x = _mx_layer_forward(self, st, i, x, layer_params(layer)) if mx else _LayerStage.apply(self, st, i, x, *layer_params(layer))
         if st.fill_event is not None:
             # the gradient buffer belongs to the MAIN stream's pool: if the graph is dropped without a backward (a validation
             # pass run in grad mode) its block may be handed out again, so the main stream must have seen the fill complete.

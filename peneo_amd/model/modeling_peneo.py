@@ -184,6 +184,22 @@ class PEneoModel(PEneoPreTrainedModel):
         self.peneo_decoder.set_pair_heads_format(fmt)
         return self
 
+    def set_encoder_format(self, fmt: str) -> "PEneoModel":
+        """"bf16" (default) or "mxfp8": the MXFP8 inference path of the backbone's encoder layers (LayoutLMv3Model.set_encoder_format;
+        eval forwards without gradients only).  Independent of set_pair_heads_format.  "mxfp8" needs compute dtype torch.bfloat16 and
+        the LayoutLMv3 backbone: LiLT's two-stream layer has no MXFP8 form and raises ValueError."""
+        if not hasattr(self.backbone, "set_encoder_format"):
+            if fmt == "mxfp8":
+                raise ValueError("mxfp8 encoder layers exist for the LayoutLMv3 backbone only, not for LiLT")
+            if fmt != "bf16":
+                raise ValueError(f"unknown encoder format {fmt!r} (expected 'bf16' or 'mxfp8')")
+            return self
+        if fmt == "mxfp8" and self._compute_dtype != torch.bfloat16:
+            raise ValueError("mxfp8 encoder layers need set_compute_dtype(torch.bfloat16) first")
+        self.backbone.compute_dtype = self._compute_dtype
+        self.backbone.set_encoder_format(fmt)
+        return self
+
     def _init_weights(self, module) -> None:
         self.backbone._init_weights(module)
 
@@ -195,6 +211,9 @@ class PEneoModel(PEneoPreTrainedModel):
                                  "with set_pair_heads_format('bf16')")
             if self._compute_dtype != torch.bfloat16:
                 raise ValueError("mxfp8 pair heads need compute dtype torch.bfloat16")
+        if getattr(self.backbone, "encoder_format", "bf16") == "mxfp8":
+            self.backbone.compute_dtype = self._compute_dtype
+            self.backbone.check_encoder_format()      # refused before anything runs, as above
         kwargs.update({"input_ids": input_ids, "bbox": bbox, "orig_bbox": orig_bbox, "attention_mask": attention_mask,
                        "image": image})
         reset_pending()   # joins left behind by a backward that raised (engine.py)

@@ -679,6 +679,97 @@ def mxfp8_quantize_rows(src: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     return q, sc
 
 
+def mxfp8_quantize_rows_bf16(src: torch.Tensor, q: Optional[torch.Tensor] = None,
+                             scales: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """mxfp8_quantize_rows for a bf16 source [rows, cols] (row stride % 8 == 0): the bytes the fp32 quantizer gives on the same values."""
+    assert src.dtype == torch.bfloat16 and src.dim() == 2 and src.stride(1) == 1
+    rows, cols = src.shape
+    if q is None:
+        q = torch.empty((rows, cols), dtype=torch.uint8, device=src.device)
+    if scales is None:
+        scales = torch.empty((rows, cols // 32), dtype=torch.uint8, device=src.device)
+    assert q.dtype == torch.uint8 and q.shape == (rows, cols) and q.is_contiguous()
+    assert scales.dtype == torch.uint8 and scales.shape == (rows, cols // 32) and scales.is_contiguous()
+    check(lib().peneo_mxfp8_quantize_rows_bf16(ptr(src), rows, cols, src.stride(0), ptr(q), ptr(scales), stream()),
+          "peneo_mxfp8_quantize_rows_bf16")
+    return q, scales
+
+
+def layernorm_mxfp8_supported(H: int) -> bool:
+    """True when layernorm_fwd_mxfp8 holds this row length (host-side, no GPU call): H % 256 == 0, H <= 1024."""
+    return bool(lib().peneo_layernorm_mxfp8_supported(int(H)))
+
+
+def layernorm_fwd_mxfp8(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float):
+    """layernorm_fwd of a contiguous bf16 [rows, H] plus the MX copy of its output in the same launch:
+    returns (y, mean, rstd, y_q, y_s) with (y_q, y_s) == mxfp8_quantize_rows_bf16(y)."""
+    assert x.dtype == torch.bfloat16 and x.dim() == 2 and x.is_contiguous()
+    rows, H = x.shape
+    y = torch.empty_like(x)
+    mean = torch.empty(rows, dtype=torch.float32, device=x.device)
+    rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
+    q = torch.empty((rows, H), dtype=torch.uint8, device=x.device)
+    sc = torch.empty((rows, H // 32), dtype=torch.uint8, device=x.device)
+    check(lib().peneo_layernorm_fwd_mxfp8(ptr(x), ptr(y), ptr(gamma), ptr(beta), eps, ptr(mean), ptr(rstd), rows, H, ptr(q), ptr(sc),
+                                          stream()), "peneo_layernorm_fwd_mxfp8")
+    return y, mean, rstd, q, sc
+
+
+def gemm_mxfp8_supported(M: int, N: int, K: int) -> bool:
+    """True when peneo_gemm_mxfp8 holds this shape (host-side, no GPU call): M >= 1, N % 32 == 0, K % 128 == 0."""
+    return bool(lib().peneo_gemm_mxfp8_supported(int(M), int(N), int(K)))
+
+
+def gemm_mxfp8(a_q: torch.Tensor, a_s: torch.Tensor, b_q: torch.Tensor, b_s: torch.Tensor, *,
+               bias: Optional[torch.Tensor] = None, act: int = ACT_NONE, residual: Optional[torch.Tensor] = None,
+               alpha: float = 1.0, out: Optional[torch.Tensor] = None, out_dtype: torch.dtype = torch.bfloat16,
+               store_c: bool = True, mx_out: bool = False):
+    """C = epilogue(A^ B^^T) on the block-scaled FP8 MFMA: a_q [M, K] / b_q [N, K] e4m3 bytes (uint8) with a_s [M, K / 32] /
+    b_s [N, K / 32] E8M0 bytes, as mxfp8_quantize_rows writes them.  Returns C (bf16 or fp32); with mx_out=True returns
+    (C, C_q, C_s), the MX quantization of the bf16-rounded result along N, and C is None when store_c=False."""
+    for t in (a_q, a_s, b_q, b_s):
+        assert t.dtype == torch.uint8 and t.dim() == 2 and t.is_contiguous()
+    M, K = a_q.shape
+    N, Kb = b_q.shape
+    assert K == Kb, f"inner dims differ: {K} vs {Kb}"
+    assert a_s.shape == (M, K // 32) and b_s.shape == (N, K // 32)
+    assert store_c or mx_out, "gemm_mxfp8: nothing to write"
+    c_dtype = out.dtype if out is not None else out_dtype
+    if store_c and out is None:
+        out = torch.empty((M, N), dtype=c_dtype, device=a_q.device)
+    if out is not None:
+        assert store_c and out.shape == (M, N) and out.stride(1) == 1
+    ep = hip.GemmEpilogue()
+    if bias is not None:
+        assert bias.dtype == torch.float32 and bias.numel() == N and bias.is_contiguous()
+    ep.bias = ptr(bias)
+    ep.act = act
+    if residual is not None:
+        assert residual.dtype == c_dtype and residual.shape == (M, N) and residual.stride(1) == 1
+        ep.residual, ep.ld_res = ptr(residual), residual.stride(0)
+    ep.alpha = alpha
+    c_q = torch.empty((M, N), dtype=torch.uint8, device=a_q.device) if mx_out else None
+    c_s = torch.empty((M, N // 32), dtype=torch.uint8, device=a_q.device) if mx_out else None
+    check(lib().peneo_gemm_mxfp8(M, N, K, ptr(a_q), ptr(a_s), ptr(b_q), ptr(b_s), ptr(out), out.stride(0) if out is not None else N,
+                                 dtype_code(c_dtype), C.byref(ep), ptr(c_q), ptr(c_s), stream()), "peneo_gemm_mxfp8")
+    return (out, c_q, c_s) if mx_out else out
+
+
+def encoder_layer_mxfp8_supported(rows: int, H: int, I: int) -> bool:
+    """True when the four products of an encoder layer (rows x 3H x H, rows x H x H, rows x I x H, rows x H x I) all pass
+    gemm_mxfp8_supported (host-side, no GPU call)."""
+    return bool(lib().peneo_encoder_layer_mxfp8_supported(int(rows), int(H), int(I)))
+
+
+def encoder_layer_fwd_mxfp8(layer: "hip.EncoderLayer", mx: "hip.EncoderLayerMxfp8", out: torch.Tensor) -> torch.Tensor:
+    """One C call for the MXFP8 inference forward of an encoder layer (include/peneo_hip.h, peneo_encoder_layer_fwd_mxfp8):
+    `layer` / `mx` hold device pointers of buffers the caller keeps alive; out [rows, H] bf16 is written and returned."""
+    assert out.dtype == torch.bfloat16 and out.is_contiguous()
+    with kernel_timer("encoder_layer_fwd_mxfp8"):
+        check(lib().peneo_encoder_layer_fwd_mxfp8(C.byref(layer), C.byref(mx), ptr(out), stream()), "peneo_encoder_layer_fwd_mxfp8")
+    return out
+
+
 def pair_mxfp8_supported(D: int, num_heads: int) -> bool:
     """True when the MXFP8 pair-heads kernel holds this shape (host-side, no GPU call)."""
     return bool(lib().peneo_pair_mxfp8_supported(int(D), int(num_heads)))
