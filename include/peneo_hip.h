@@ -654,6 +654,31 @@ int peneo_spots_to_tags(const int32_t* spots_bijt, int n_spots, int B, int N, in
 int peneo_spots_compact(const float* logits, int64_t P, int C, int N, int32_t* spots_ijt, float* scores,
                         int32_t* count, int max_spots, peneo_stream_t stream);
 
+/* K14, batched: every map of a batch in ONE call (two stream-ordered launches: count, then write; csrc/spots.hip) — replaces one
+ * peneo_spots_compact launch and one host read of its count per document and head (HandshakingTaggingScheme.
+ * get_spots_from_shaking_tag, model/peneo_decoder.py:76-115, called 5 x B times per batch by pipeline/decode.py).
+ * Map m is fp32 logits [B, P, classes[m]] (classes[m] >= 2) or an int64 label map [B, P] (classes[m] == 0); P = N (N + 1) / 2,
+ * the same B and N for every map.  Per (map, document), exactly peneo_spots_compact: tag = first maximum under strict > (ties to
+ * the lower class, a NaN never wins), score = 1 / sum_c exp(l_c - max) (the same bits), a pair is a spot iff tag != 0, spots come
+ * out in increasing p; a label map's spot is value != 0 (the int64 value) with tag = value and score 1.0; labels are expected in the int32
+ * range: a value outside it is still a spot, its tag is the low 32 bits (1 where those are zero).
+ *   records [num_maps][B][max_spots] of 16 bytes {int32 i, int32 j, int32 tag, float score}, 16-byte aligned;
+ *   counts  [num_maps][B] int32: the TRUE number of spots, which may exceed max_spots; only the first max_spots in p order are
+ *           stored and nothing is written behind a (map, document)'s min(count, max_spots) records.
+ * workspace: peneo_spots_compact_batch_workspace_bytes(num_maps, B, N) bytes (the per-segment counts; 0 = shape out of range),
+ * 4-byte aligned, used by one call at a time.  The caller owns every buffer; no allocation and no host synchronisation inside.
+ * PENEO_ERR_INVALID, with nothing launched: a NULL map / records / counts, num_maps outside 1 .. PENEO_MAX_HEADS, classes[m] == 1
+ * or < 0, a NULL or short workspace, max_spots < 0, B < 1 or B > 65535 (documents are one grid dimension), N < 1 or N > 65535 (P must stay below 2^31).  records may be
+ * NULL when max_spots == 0 (count only). */
+typedef struct peneo_spots_batch_desc {
+  int num_maps;                          /* <= PENEO_MAX_HEADS */
+  int classes[PENEO_MAX_HEADS];          /* >= 2: fp32 logits [B, P, classes[m]]; 0: int64 label map [B, P] */
+  const void* maps[PENEO_MAX_HEADS];
+} peneo_spots_batch_desc;
+size_t peneo_spots_compact_batch_workspace_bytes(int num_maps, int B, int N);
+int peneo_spots_compact_batch(const peneo_spots_batch_desc* desc, int B, int N, void* records, int32_t* counts,
+                              int max_spots, void* workspace, size_t workspace_bytes, peneo_stream_t stream);
+
 /* ---- diagnostics: NOT part of the thread-safety contract -------------------------------------------------------------
  * Process-wide switch of the forward GEMM tile choice (gemm_big.hip): 0 = always the 128 x 128 kernel, 1 = the calibrated
  * choice (default; also set by PENEO_GEMM_BIG), 256 / 384 / 128 = force one big-tile shape where its constraints hold.  A plain

@@ -343,4 +343,20 @@ __device__ __forceinline__ void pair_decode(int64_t p, int n, int& i, int& j) {
   j = ii + (int)(p - pair_row_start(ii, n));
 }
 
+// ---------------------------------------------------------------- spot decode (K14): one pair's class row -> (tag, score)
+// tag = first index of the maximum under strict > (ties go to the lower class; a NaN never wins, and a NaN in class 0 keeps tag 0);
+// score = softmax probability of the tag = 1 / sum_c exp(l_c - max), summed in class order.  The per-map kernel (pair_heads.hip) and
+// the batched one (spots.hip) both call these, so their tags and scores are the same bits.
+__device__ __forceinline__ int spot_argmax(const float* l, int C, float& mx) {
+  mx = l[0];
+  int am = 0;
+  for (int c = 1; c < C; ++c) if (l[c] > mx) { mx = l[c]; am = c; }
+  return am;
+}
+__device__ __forceinline__ float spot_score(const float* l, int C, float mx) {
+  float se = 0.f;
+  for (int c = 0; c < C; ++c) se += __expf(l[c] - mx);
+  return 1.f / se;
+}
+
 }  // namespace peneo

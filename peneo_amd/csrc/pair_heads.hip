@@ -731,11 +731,9 @@ __global__ __launch_bounds__(1024) void spots_compact_kernel(const float* logits
     int tag = 0; float sc = 0.f;
     if (pp < P) {
       const float* l = logits + pp * C;
-      float mx = l[0]; int am = 0;
-      for (int c = 1; c < C; ++c) if (l[c] > mx) { mx = l[c]; am = c; }
-      float se = 0.f;
-      for (int c = 0; c < C; ++c) se += __expf(l[c] - mx);
-      tag = am; sc = 1.f / se;
+      float mx;
+      tag = spot_argmax(l, C, mx);
+      sc = spot_score(l, C, mx);
     }
     const unsigned long long bal = __ballot(tag != 0);
     const int before = __popcll(bal & ((1ull << lane) - 1ull));

@@ -94,6 +94,10 @@ class PairDzArgs(C.Structure):
                 ("drop_pair0", _i64)]
 
 
+class SpotsBatchDesc(C.Structure):
+    _fields_ = [("num_maps", _i), ("classes", _i * MAX_HEADS), ("maps", _vp * MAX_HEADS)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/peneo_hip.h appears here
 SIGNATURES = {
     "peneo_version": (_i, []),
@@ -185,6 +189,8 @@ SIGNATURES = {
     "peneo_encoder_layer_bwd": (_i, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp]),
     "peneo_spots_to_tags": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
     "peneo_spots_compact": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp, _i, _vp]),
+    "peneo_spots_compact_batch_workspace_bytes": (_sz, [_i, _i, _i]),
+    "peneo_spots_compact_batch": (_i, [C.POINTER(SpotsBatchDesc), _i, _i, _vp, _vp, _i, _vp, _sz, _vp]),
     "peneo_gemm_set_big_mode": (None, [_i]),    # diagnostics block of the header: process-wide, not thread-safe
     "peneo_gemm_set_sk_mode": (None, [_i]),
     "peneo_gemm_sk_set_prof": (None, [_vp]),

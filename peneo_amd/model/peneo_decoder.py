@@ -73,6 +73,8 @@ class HandshakingTaggingScheme:
         """[P, C] logits (or [P] tags) -> [(i, j, tag, score)] in increasing p order (reference :76-115).
         Device tensors go through the fused softmax/argmax/compaction kernel (K14) — one launch and one
         copy instead of a Python loop with three ``.item()`` syncs per spot."""
+        if isinstance(shaking_tag, list):   # already compacted (get_spots_from_shaking_tags_batch): the spot list itself
+            return shaking_tag
         if shaking_ind2matrix_ind is None and seq_len is None:
             raise ValueError("If shaking_ind2matrix_ind and matrix_ind2shaking_ind are not provided,seq_len must be given")
         P = shaking_tag.shape[0]
@@ -100,6 +102,38 @@ class HandshakingTaggingScheme:
                     i += 1
                 j = i + p - (i * n - i * (i - 1) // 2)
             out.append((i, j, int(pred[p]), float(score[p])))
+        return out
+
+    @staticmethod
+    def get_spots_from_shaking_tags_batch(maps: Sequence[torch.Tensor], seq_len: int):
+        """Every map of a batch at once: ``maps[m]`` is [B, P, C] logits or a [B, P] label map; returns ``out[m][b]`` =
+        ``get_spots_from_shaking_tag(maps[m][b], seq_len=seq_len)``.  Device maps that are floating [B, P, C >= 2] logits or
+        integer [B, P] / [B, P, 1] labels take one batched compaction call (``ops.spots_compact_batch``: two launches and two
+        device-to-host copies for the whole batch, up to 8 maps a call) instead of one launch and three copies per document
+        and map; every other map (host tensors, floating label maps) takes the per-document call itself."""
+        get = HandshakingTaggingScheme.get_spots_from_shaking_tag
+        out: List[Optional[list]] = [None] * len(maps)
+        dev_maps, dev_at = [], []
+        for k, m in enumerate(maps):
+            logits = torch.is_tensor(m) and m.is_cuda and m.dim() == 3 and m.shape[-1] > 1 and m.is_floating_point()
+            labels = torch.is_tensor(m) and m.is_cuda and not m.is_floating_point() and not m.is_complex() and \
+                (m.dim() == 2 or (m.dim() == 3 and m.shape[-1] == 1))
+            if logits or labels:
+                dev_maps.append(m.float().contiguous() if logits else m.reshape(m.shape[0], m.shape[1]).long().contiguous())
+                dev_at.append(k)
+            else:
+                out[k] = [get(m[b], seq_len=seq_len) for b in range(len(m))]
+        for m0 in range(0, len(dev_maps), ops.hip.MAX_HEADS):
+            records, counts = ops.spots_compact_batch(dev_maps[m0:m0 + ops.hip.MAX_HEADS], seq_len)
+            # column by column: a [n, 3] tolist() makes n short lists at once, and the collector walks them again and again
+            spots = list(zip(records[:, 0].tolist(), records[:, 1].tolist(), records[:, 2].tolist(),
+                             records.view(torch.float32)[:, 3].tolist()))
+            at = 0
+            for k, per_doc in zip(dev_at[m0:], counts.tolist()):
+                out[k] = []
+                for n in per_doc:
+                    out[k].append(spots[at:at + n])
+                    at += n
         return out
 
 

@@ -1005,6 +1005,69 @@ def spots_compact(logits: torch.Tensor, N: int, max_spots: int = 4096):
     return spots[:n], scores[:n]
 
 
+def spots_batch_workspace_bytes(num_maps: int, B: int, N: int) -> int:
+    return int(lib().peneo_spots_compact_batch_workspace_bytes(num_maps, B, N))
+
+
+def spots_compact_batch_launch(maps, N: int, max_spots: int, records: Optional[torch.Tensor] = None,
+                               counts: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None):
+    """The two launches of ``peneo_spots_compact_batch`` on the current stream, no host synchronisation.  ``maps``: fp32
+    logits [B, P, C] (C >= 2) and / or int64 label maps [B, P], all of one B and P = N (N + 1) / 2, contiguous.  Returns the
+    device tensors (records int32 [M, B, max_spots, 4] = (i, j, tag, score bits), counts int32 [M, B])."""
+    M = len(maps)
+    if not 1 <= M <= hip.MAX_HEADS:
+        raise hip.PeneoHipError(f"spots_compact_batch: {M} maps (1 .. {hip.MAX_HEADS} per call)")
+    B, P = maps[0].shape[0], maps[0].shape[1]
+    dev = maps[0].device
+    desc = hip.SpotsBatchDesc()
+    desc.num_maps = M
+    for m, t in enumerate(maps):
+        label = t.dtype == torch.int64 and t.dim() == 2
+        if not (label or (t.dtype == torch.float32 and t.dim() == 3)) or tuple(t.shape[:2]) != (B, P) or t.device != dev:
+            raise hip.PeneoHipError(f"spots_compact_batch: map {m} is {t.dtype} {tuple(t.shape)}; want fp32 [{B}, {P}, C] or int64 [{B}, {P}]")
+        if P != N * (N + 1) // 2:
+            raise hip.PeneoHipError(f"spots_compact_batch: P = {P} is not N (N + 1) / 2 for N = {N}")
+        desc.classes[m] = 0 if label else t.shape[2]
+        desc.maps[m] = ptr(_c(t))
+    max_spots = int(max_spots)
+    if records is None:   # (an empty tensor has no storage: max_spots == 0 counts only and hands the library a NULL records)
+        records = torch.empty((M, B, max_spots, 4), dtype=torch.int32, device=dev)
+    if counts is None:
+        counts = torch.empty((M, B), dtype=torch.int32, device=dev)
+    need = spots_batch_workspace_bytes(M, B, N)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    if records.dtype != torch.int32 or records.numel() < M * B * max_spots * 4 or counts.dtype != torch.int32 or \
+            counts.numel() < M * B or records.device != dev or counts.device != dev or workspace.device != dev:
+        raise hip.PeneoHipError(f"spots_compact_batch: records / counts must be int32 tensors on {dev} holding "
+                                f"{M * B * max_spots} records and {M * B} counts")
+    check(lib().peneo_spots_compact_batch(C.byref(desc), B, N, ptr(_c(records)) if max_spots else None, ptr(_c(counts)), max_spots,
+                                          ptr(_c(workspace)), workspace.numel() * workspace.element_size(), stream()),
+          "peneo_spots_compact_batch")
+    return records, counts
+
+
+def spots_compact_batch(maps, N: int, max_spots: int = 4096):
+    """Every map of a batch in one call (``spots_compact_batch_launch``) and two device-to-host copies, whatever B and the
+    number of maps: the counts, then the stored records alone, packed on the device.  Returns HOST tensors (records int32
+    [total, 4] = (i, j, tag, score bits; view as float32), counts int32 [M, B]): the spots of document b of map m are the
+    ``counts[m, b]`` rows behind those of the (map, document)s before it, in increasing p order.  A count above ``max_spots``
+    repeats the launches once with the largest count."""
+    max_spots = max(int(max_spots), 1)
+    records, counts = spots_compact_batch_launch(maps, N, max_spots)
+    counts_h = counts.cpu()
+    k, total = int(counts_h.max()), int(counts_h.sum())
+    if k > max_spots:
+        max_spots = k
+        records, _ = spots_compact_batch_launch(maps, N, max_spots)
+    # packed row r belongs to the (map, document) d whose running total first exceeds r, at slot r - (the total before d)
+    c = counts.view(-1).long()
+    end = c.cumsum(0)
+    r = torch.arange(total, device=records.device)
+    d = torch.searchsorted(end, r, right=True)
+    return records.view(-1, 4).index_select(0, d * max_spots + r - (end - c)[d]).cpu(), counts_h
+
+
 def spots_to_tags(batch_spots, N: int, device, B: int = None) -> torch.Tensor:
     """Sparse spots -> dense label maps [B, P] int64 built on the device (K13 input side).  ``batch_spots``: a list with
     one [(i, j, tag), ...] list per document, or an int32 tensor [n, 4] of (b, i, j, tag) rows (then ``B`` is required;

@@ -6,7 +6,9 @@ BASELINE config 1 exercises end to end (RFUND json -> ``RFUNDDataset`` -> ``Data
 ``decode_peneo`` -> ``calculate_KVPE_metric``), so it is restated here without the Trainer: the same per-batch reads of the
 model output (``orig_bbox.tolist()``, the five score maps split along the batch dimension, ``<x>_loss.mean().item()`` of
 the LAST batch), the same arguments to ``decode_peneo`` and the same metric keys.  The score maps stay on the device: the
-decode front end (``peneo_spots_compact``) reduces each ``[P, C]`` map to its few spots there."""
+decode front end (``peneo_spots_compact``) reduces each ``[P, C]`` map to its few spots there.  ``compact_spots=True`` does that
+reduction batch by batch (``peneo_spots_compact_batch``) and keeps only the spot lists, so the loop's device memory does not grow
+with the number of documents."""
 from __future__ import annotations
 
 from typing import Callable, Dict, Iterable, List, Optional
@@ -56,11 +58,17 @@ def make_compute_metrics(detail_eval: bool = False, start_eval_epoch: int = 0,
 
 @torch.no_grad()
 def prediction_loop(model, dataloader: Iterable[Dict[str, object]], compute_metrics: Optional[Callable] = None,
-                    epoch: int = 0, metric_key_prefix: str = "eval", device=None) -> Dict[str, float]:
+                    epoch: int = 0, metric_key_prefix: str = "eval", device=None, compact_spots: bool = False) -> Dict[str, float]:
     """One pass over ``dataloader`` (batches of ``DataCollatorForPEneo``) in eval mode; returns the metric dict with every
     key prefixed ``<prefix>_`` (pipeline/trainer.py:57-211).  As in the reference the reported losses are those of the last
     batch, and ``<prefix>_line_grouping_h2h_loss`` ends up holding the tail->tail loss (:196-201 assigns that key twice);
-    callers that want the separate values read them from the model output."""
+    callers that want the separate values read them from the model output.
+
+    ``compact_spots=False`` (default) hands ``compute_metrics`` the score maps and label maps of every document as tensors, as
+    the reference does.  ``compact_spots=True`` compacts the five score maps of each batch right after its forward, and the
+    five label maps the same way (sparse labels through ``ops.spots_to_tags`` first, which keeps "last spot wins"), drops the
+    tensors and hands ``compute_metrics`` spot lists ``[(i, j, tag, score)]`` in their place; ``decode_peneo`` /
+    ``sample_decode_peneo`` take either, and the metrics are the same."""
     if device is None:
         device = next(model.parameters()).device
     compute_metrics = compute_metrics or make_compute_metrics()
@@ -72,7 +80,7 @@ def prediction_loop(model, dataloader: Iterable[Dict[str, object]], compute_metr
     relations: List[list] = []
     maps: List[List[torch.Tensor]] = [[] for _ in _OUTPUTS]
     tags: List[List[torch.Tensor]] = [[] for _ in _TAGS]
-    outputs = None
+    losses = None
     for batch in dataloader:
         if "text" not in batch:
             raise ValueError("No text given in evaluation")
@@ -82,24 +90,33 @@ def prediction_loop(model, dataloader: Iterable[Dict[str, object]], compute_metr
         text += batch["text"]
         file_ids += batch.get("fname", [])
         relations += batch["relations"]
-        for k, name in enumerate(_OUTPUTS):
-            maps[k] += list(getattr(outputs, name + "_shaking_outputs"))
-        for k, name in enumerate(_TAGS):
+        N = outputs.orig_bbox.shape[1]
+        batch_maps = [getattr(outputs, name + "_shaking_outputs") for name in _OUTPUTS]
+        batch_tags = []
+        for name in _TAGS:
             key = name + "_shaking_tag"
             if key in batch:
-                tags[k] += list(batch[key])
+                batch_tags.append(inputs[key] if compact_spots else batch[key])
             else:  # sparse labels: rebuild the per-document maps on the device for the ground-truth side of the decode
                 from .. import ops
-                B, N = inputs["input_ids"].shape[0], outputs.orig_bbox.shape[1]
-                tags[k] += list(ops.spots_to_tags(inputs[name + "_matrix_spots"], N, device, B=B))
+                batch_tags.append(ops.spots_to_tags(inputs[name + "_matrix_spots"], N, device, B=inputs["input_ids"].shape[0]))
+        if compact_spots:   # tensors -> spot lists now
+            batch_maps = HandshakingTaggingScheme.get_spots_from_shaking_tags_batch(batch_maps, N)
+            batch_tags = HandshakingTaggingScheme.get_spots_from_shaking_tags_batch(batch_tags, N)
+        for k in range(len(_OUTPUTS)):
+            maps[k] += list(batch_maps[k])
+            tags[k] += list(batch_tags[k])
+        # the reported losses are the last batch's; the output object (it holds the five score maps) and this batch's tensors go
+        # before the next forward runs, so with compact_spots no map outlives its iteration
+        losses = (outputs.loss, outputs.line_extraction_loss, outputs.ent_linking_h2h_loss, outputs.ent_linking_t2t_loss,
+                  outputs.line_grouping_t2t_loss)
+        del outputs, inputs, batch_maps, batch_tags
     model.train(was_training)
-    if outputs is None:
+    if losses is None:
         return {}
     metrics = dict(compute_metrics((tuple(maps), (*tags, relations, orig_bboxes, text), file_ids), epoch))
     pre = metric_key_prefix + "_"
-    metrics[pre + "loss"] = outputs.loss.mean().item()
-    metrics[pre + "line_extraction_loss"] = outputs.line_extraction_loss.mean().item()
-    metrics[pre + "ent_linking_h2h_loss"] = outputs.ent_linking_h2h_loss.mean().item()
-    metrics[pre + "ent_linking_t2t_loss"] = outputs.ent_linking_t2t_loss.mean().item()
-    metrics[pre + "line_grouping_h2h_loss"] = outputs.line_grouping_t2t_loss.mean().item()
+    for key, loss in zip(("loss", "line_extraction_loss", "ent_linking_h2h_loss", "ent_linking_t2t_loss", "line_grouping_h2h_loss"),
+                         losses):
+        metrics[pre + key] = loss.mean().item()
     return {(k if k.startswith(pre) else pre + k): v for k, v in metrics.items()}
