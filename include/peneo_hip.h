@@ -311,6 +311,29 @@ int peneo_attn_bwd(int dtype, const void* q, const void* k, const void* v, int64
                    void* dq, void* dk, void* dv, int64_t ld_dqkv, float* g_bias, float* delta, float* dq_accum,
                    void* ds_out, float drop_p, const uint32_t* drop_words, peneo_stream_t stream);
 
+/* Two-stream attention forward (version 103): LiLT's attention (modeling_lilt.py:269-429) as ONE call - two operand streams
+ * (text a, layout b), one shared softmax, two outputs - without the packed copies of peneo_head_concat / peneo_head_split:
+ *   scores[b,h,i,j] = (scale_a * q_a) . k_a + (scale_b * q_b) . k_b + key_bias[b,j]
+ *   P = softmax over the keys j < T;   out_a = P . v_a,   out_b = P . v_b
+ * q_a / k_a / v_a are rows of a [B*T, ld_a] matrix with head h at columns h*d_a.., q_b / k_b / v_b rows of a [B*T, ld_b] matrix with
+ * head h at columns h*d_b.. (e.g. column slices of the two fused QKV buffers); out_a / out_b likewise with ld_out_a / ld_out_b.
+ * scale_a * q_a and scale_b * q_b are rounded to bf16 before the products, which is what peneo_head_concat writes (exact for powers
+ * of two), so the results equal peneo_head_concat x 2 -> peneo_attn_fwd(d = d_a + d_b, scale 1, no bias tensor, key_bias) ->
+ * peneo_head_split bit for bit.  key_bias: fp32 [B, Tp], Tp = peneo_attn_padded_len(T), additive (0 / -1e30), may be NULL; keys
+ * j >= T are masked by the kernel itself and nothing is promised about, or read from, its padding columns [T, Tp).  A query row
+ * whose keys are all masked gives zeros and lse = -1e30, as peneo_attn_fwd does.  lse: fp32 [B, nh, T] in log2 units, the format of
+ * peneo_attn_fwd (so that a backward can use it); may be NULL.  No workspace, no allocation, no dropout.
+ * peneo_attn2_supported is a host-side question (no GPU call): 1 for (PENEO_BF16, 64, 16), 0 for everything else.
+ * peneo_attn2_fwd returns PENEO_ERR_INVALID (with a peneo_last_error text, nothing launched, never a silent fallback) for an
+ * unsupported triple, B / nh / T below 1, a null operand or output, an operand or output pointer that is not 16-byte aligned, a row
+ * stride whose byte size is not a multiple of 16 or is too small for nh heads, and strides or T whose tile offsets do not fit the
+ * kernel's 32-bit lane offsets. */
+int peneo_attn2_supported(int dtype, int d_a, int d_b);
+int peneo_attn2_fwd(int dtype, const void* q_a, const void* k_a, const void* v_a, int64_t ld_a,
+                    const void* q_b, const void* k_b, const void* v_b, int64_t ld_b,
+                    int B, int nh, int T, int d_a, int d_b, float scale_a, float scale_b, const float* key_bias,
+                    void* out_a, int64_t ld_out_a, void* out_b, int64_t ld_out_b, float* lse, peneo_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * K11 + K12 (+ K13) — handshaking + the pair-classifier heads + class-weighted CE, fused
  * (model/peneo_decoder.py:149-177, 231-292, 315-336, 355-428; model/custom_loss.py:189-202).

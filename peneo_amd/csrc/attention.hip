@@ -468,12 +468,15 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 && DP <= 64) ? (FK == 32 ? 3 :
   // normalise and write O[q, d] through LDS (transpose to row-major rows)
   __syncthreads();
   float* myO = reinterpret_cast<float*>(smem) + wave * 32 * (DP + 1);
+  // `any`: some key of the row is not masked.  With every key at -1e30 the running maximum is -1e30 too and the exponent
+  // fmaf(s, LOG2E, nm) is the rounding error of that product, up to 2^76 of either sign: P can be inf and O inf - inf
   const bool any = m_run > 0.5f * MASKED;
   const float inv = (any && l_run > 0.f) ? keep_scale / l_run : 0.f;
 #pragma unroll
   for (int t = 0; t < DT; ++t)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) myO[(lane & 31) * (DP + 1) + t * 32 + acc_row(r, lane)] = o[t][r] * inv;
+    for (int r = 0; r < 16; ++r)   // (a row whose keys are all masked: zeros - its accumulators can hold inf / NaN, see `any`)
+      myO[(lane & 31) * (DP + 1) + t * 32 + acc_row(r, lane)] = any ? o[t][r] * inv : 0.f;
   if (half == 0 && myq < Tn && p.lse) p.lse[((int64_t)b * p.nh + h) * Tn + myq] = any ? fmaf(m_run, LOG2E, log2f(l_run)) : MASKED;  // log2 units
   __syncthreads();
   T* O = reinterpret_cast<T*>(p.out) + (int64_t)b * Tn * p.ld_out + h * d;

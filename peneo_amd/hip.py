@@ -141,6 +141,9 @@ SIGNATURES = {
     "peneo_attn_drop_words": (_i, [_vp, _i, _i, _i, _f, _u32, _vp]),
     "peneo_attn_bwd": (_i, [_i, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i, _i, _i, _i, _f, _vp, _i64, _vp,
                             _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _f, _vp, _vp]),
+    "peneo_attn2_supported": (_i, [_i, _i, _i]),
+    "peneo_attn2_fwd": (_i, [_i, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _f, _f, _vp, _vp, _i64, _vp, _i64,
+                             _vp, _vp]),
     "peneo_pair_heads_packed_bytes": (_sz, [_i, _i, _i]),
     "peneo_pair_heads_pack": (_i, [_i, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "peneo_pair_heads_fwd": (_i, [_i, _vp, _i, _i, C.POINTER(PairHeadsDesc), _vp, C.POINTER(PairLoss), _vp]),

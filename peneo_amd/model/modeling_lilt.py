@@ -154,6 +154,7 @@ class _State:
         self.seeds = None
         self.dtype = torch.float32
         self.dims = None
+        self.attn2 = False        # this forward's attention runs as the two-stream kernel (_use_attn2)
 
 
 class _LiltEmbedStage(torch.autograd.Function):
@@ -317,6 +318,14 @@ def _post_attn_bwd2(wc, idx, dt, seeds, site_t, site_l, d_out, d_lout, sv_t, sv_
     return d_att, d_h1, gt, d_latt, d_lh1, gl, wg_t, wg_l
 
 
+def _use_attn2(dt, seeds, d, dl) -> bool:
+    """The two-stream attention forward (ops.attn2_fwd) instead of head_concat x 2 + attn_fwd + head_split: forwards without
+    autograd and without attention dropout, where the kernel takes the widths.  It is bit-identical to the path it replaces
+    (tests/test_gpu_attn2.py); PENEO_LILT_ATTN2=0, read at call time, keeps the concat path."""
+    return (dt == torch.bfloat16 and not torch.is_grad_enabled() and seeds.p_attn <= 0.0 and ops.attn2_supported(dt, d, dl)
+            and os.environ.get("PENEO_LILT_ATTN2", "1") != "0")
+
+
 class _LiltLayerStage(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, st, idx, x, l, *params):
@@ -342,6 +351,19 @@ class _LiltLayerStage(torch.autograd.Function):
             qkv = ops.gemm(x, Wqkv, bias=bqkv)          # [R, 3H]
             lqkv = ops.gemm(l, Wlqkv, bias=blqkv)       # [R, 3Hl]
         R = x.shape[0]
+        if st.attn2:
+            # no autograd, no attention dropout (LiltModel.forward decided): the two-stream kernel reads q | k | v where the QKV GEMMs
+            # left them and writes both context streams - no packed copy `cat`, no `attc`, nothing saved for a backward
+            att = torch.empty((R, H), dtype=dt, device=dev)
+            latt = torch.empty((R, Hl), dtype=dt, device=dev)
+            ops.attn2_fwd(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], lqkv[:, :Hl], lqkv[:, Hl:2 * Hl], lqkv[:, 2 * Hl:], B, nh, S,
+                          1.0 / math.sqrt(d), 1.0 / math.sqrt(dl), st.key_bias, out_a=att, out_b=latt)
+            if grouped:
+                xo, lo, _, _ = _post_attn_fwd2(wc, idx, dt, cfg.layer_norm_eps, seeds, site + 2, site + 6, x, att, tp, l, latt, lp)
+            else:
+                xo, _ = _post_attn_fwd(wc, f"L{idx}.t", dt, cfg.layer_norm_eps, seeds, site + 2, x, att, tp)
+                lo, _ = _post_attn_fwd(wc, f"L{idx}.l", dt, cfg.layer_norm_eps, seeds, site + 6, l, latt, lp)
+            return xo, lo
         cat = torch.empty((R, 3 * nh * dc), dtype=dt, device=dev)
         ops.head_concat(qkv[:, :H], lqkv[:, :Hl], nh, cat[:, :nh * dc], 1.0 / math.sqrt(d), 1.0 / math.sqrt(dl))
         ops.head_concat(qkv[:, H:], lqkv[:, Hl:], 2 * nh, cat[:, nh * dc:])      # k and v in one launch: 2 nh "heads"
@@ -546,6 +568,8 @@ class LiltModel(nn.Module):
         kb = torch.zeros((B, ops.attn_padded_len(S)), dtype=torch.float32, device=dev)
         kb[:, :S].masked_fill_(attention_mask == 0, -1.0e30)
         st.key_bias = kb
+        H, nh = cfg.hidden_size, cfg.num_attention_heads
+        st.attn2 = _use_attn2(st.dtype, st.seeds, H // nh, H // cfg.channel_shrink_ratio // nh)   # once per forward; the layers follow
         e, le = self.embeddings, self.layout_embeddings
         eparams = [e.word_embeddings.weight, e.token_type_embeddings.weight, e.position_embeddings.weight,
                    e.LayerNorm.weight, e.LayerNorm.bias, le.x_position_embeddings.weight, le.y_position_embeddings.weight,

@@ -546,6 +546,43 @@ def attn_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, B: int, nh: int,
     return out, lse
 
 
+def attn2_supported(dtype: torch.dtype, d_a: int, d_b: int) -> bool:
+    """Whether attn2_fwd takes this dtype and pair of head dims (peneo_attn2_supported: a host-side question, no GPU call)."""
+    return bool(lib().peneo_attn2_supported(dtype_code(dtype), d_a, d_b))
+
+
+def attn2_fwd(q_a: torch.Tensor, k_a: torch.Tensor, v_a: torch.Tensor, q_b: torch.Tensor, k_b: torch.Tensor, v_b: torch.Tensor,
+              B: int, nh: int, T: int, scale_a: float, scale_b: float, key_bias: Optional[torch.Tensor] = None,
+              out_a: Optional[torch.Tensor] = None, out_b: Optional[torch.Tensor] = None, lse: Optional[torch.Tensor] = None):
+    """Two-stream attention forward (LiLT): scores = (scale_a q_a).k_a + (scale_b q_b).k_b + key_bias, one softmax,
+    out_a = P v_a and out_b = P v_b.  q_a/k_a/v_a: 2-D views [B*T, nh*d_a] with a common row stride, q_b/k_b/v_b: [B*T, nh*d_b]
+    likewise (e.g. column slices of the fused qkv and lqkv buffers); key_bias: fp32 [B, Tp] additive (0 / -1e30).
+    out_a [B*T, nh*d_a], out_b [B*T, nh*d_b] (row strides may be larger) and lse [B, nh, T] may be given.
+    Returns (out_a, out_b, lse); equal bit for bit to head_concat x 2 -> attn_fwd(d_a + d_b, scale 1) -> head_split."""
+    assert q_a.dim() == 2 and q_b.dim() == 2 and q_a.shape[0] == q_b.shape[0] == B * T
+    assert q_a.dtype == k_a.dtype == v_a.dtype == q_b.dtype == k_b.dtype == v_b.dtype
+    assert q_a.stride(0) == k_a.stride(0) == v_a.stride(0) and q_a.stride(1) == k_a.stride(1) == v_a.stride(1) == 1
+    assert q_b.stride(0) == k_b.stride(0) == v_b.stride(0) and q_b.stride(1) == k_b.stride(1) == v_b.stride(1) == 1
+    assert q_a.shape == k_a.shape == v_a.shape and q_b.shape == k_b.shape == v_b.shape
+    assert q_a.shape[1] % nh == 0 and q_b.shape[1] % nh == 0
+    d_a, d_b = q_a.shape[1] // nh, q_b.shape[1] // nh
+    if out_a is None:
+        out_a = torch.empty((B * T, nh * d_a), dtype=q_a.dtype, device=q_a.device)
+    if out_b is None:
+        out_b = torch.empty((B * T, nh * d_b), dtype=q_a.dtype, device=q_a.device)
+    if lse is None:
+        lse = torch.empty((B, nh, T), dtype=torch.float32, device=q_a.device)
+    assert out_a.shape == (B * T, nh * d_a) and out_a.stride(1) == 1 and out_a.dtype == q_a.dtype
+    assert out_b.shape == (B * T, nh * d_b) and out_b.stride(1) == 1 and out_b.dtype == q_a.dtype
+    assert lse.is_contiguous() and lse.shape == (B, nh, T) and lse.dtype == torch.float32
+    if key_bias is not None:
+        assert key_bias.dtype == torch.float32 and key_bias.is_contiguous() and key_bias.shape == (B, attn_padded_len(T))
+    check(lib().peneo_attn2_fwd(dtype_code(q_a.dtype), ptr(q_a), ptr(k_a), ptr(v_a), q_a.stride(0), ptr(q_b), ptr(k_b), ptr(v_b),
+                                q_b.stride(0), B, nh, T, d_a, d_b, scale_a, scale_b, ptr(key_bias), ptr(out_a), out_a.stride(0),
+                                ptr(out_b), out_b.stride(0), ptr(lse), stream()), "peneo_attn2_fwd")
+    return out_a, out_b, lse
+
+
 def attn_bwd(q, k, v, out, d_out, lse, B: int, nh: int, T: int, d: int, scale: float, bias, key_bias,
              dqkv: torch.Tensor, g_bias: Optional[torch.Tensor], drop_p: float = 0.0, drop_seed: int = 0,
              single_pass: Optional[bool] = None, ds_out: Optional[torch.Tensor] = None,
