@@ -334,6 +334,41 @@ int peneo_attn2_fwd(int dtype, const void* q_a, const void* k_a, const void* v_a
                     int B, int nh, int T, int d_a, int d_b, float scale_a, float scale_b, const float* key_bias,
                     void* out_a, int64_t ld_out_a, void* out_b, int64_t ld_out_b, float* lse, peneo_stream_t stream);
 
+/* Two-stream attention for training (version 104): the forward with attention dropout, and the backward.
+ * peneo_attn2_fwd_dropout is peneo_attn2_fwd plus (drop_p, drop_words): drop_words is ONE set of peneo_attn_drop_words in the format
+ * peneo_attn_fwd takes; both value streams share the mask; kept probabilities are scaled by 1 / (1 - p) once, on the accumulators;
+ * lse stays the pre-dropout log-sum-exp.  drop_p == 0 with NULL words gives the bits of peneo_attn2_fwd; drop_p > 0 with NULL words
+ * is PENEO_ERR_INVALID.  With dropout it equals the concat path (peneo_attn_fwd at d_a + d_b with the same words) bit for bit.
+ *
+ * peneo_attn2_bwd writes the gradients of that contract with respect to the UNSCALED q_a, k_a, v_a, q_b, k_b, v_b (dq_a carries
+ * scale_a, dq_b scale_b: what peneo_head_split(dcat, .., scale_a, scale_b) delivers on the concat path, bit for bit for power-of-two
+ * scales).  out_a / d_out_a are rows of [B*T, ld_out_a] matrices, out_b / d_out_b of [B*T, ld_out_b]; lse is the forward's;
+ * dq_a / dk_a / dv_a are rows of a [B*T, ld_da] matrix with head h at columns h*d_a.., dq_b / dk_b / dv_b of a [B*T, ld_db] matrix
+ * (e.g. the column thirds of two fused dqkv buffers).  drop_p / drop_words: what the forward took.
+ * workspace: peneo_attn2_bwd_workspace_bytes(B, nh, T) bytes (0 for sizes below 1), 16-byte aligned, owned by the caller: delta
+ * (fp32 [B, nh, T]) then the dS^T slab (bf16 [B, nh, T keys, Tp queries]).  It needs no initialisation, carries no state between
+ * calls and may be reused by the next call on the same stream; nothing is allocated, so the call is safe under graph capture.
+ * Three launches (delta; dK, dV and the slab; dQ from the slab).  PENEO_ERR_INVALID (peneo_last_error names the function, nothing is
+ * launched, never a silent fallback) for an unsupported triple, sizes below 1, a null or misaligned operand, output or workspace,
+ * row strides that are not multiples of 16 bytes or too small for nh heads, strides or T beyond the kernels' 32-bit lane offsets,
+ * and drop_p > 0 without words. */
+int peneo_attn2_fwd_dropout(int dtype, const void* q_a, const void* k_a, const void* v_a, int64_t ld_a,
+                            const void* q_b, const void* k_b, const void* v_b, int64_t ld_b,
+                            int B, int nh, int T, int d_a, int d_b, float scale_a, float scale_b, const float* key_bias,
+                            void* out_a, int64_t ld_out_a, void* out_b, int64_t ld_out_b, float* lse,
+                            float drop_p, const uint32_t* drop_words, peneo_stream_t stream);
+size_t peneo_attn2_bwd_workspace_bytes(int B, int nh, int T);
+int peneo_attn2_bwd(int dtype,
+                    const void* q_a, const void* k_a, const void* v_a, int64_t ld_a,
+                    const void* q_b, const void* k_b, const void* v_b, int64_t ld_b,
+                    const void* out_a, const void* d_out_a, int64_t ld_out_a,
+                    const void* out_b, const void* d_out_b, int64_t ld_out_b,
+                    const float* lse, int B, int nh, int T, int d_a, int d_b, float scale_a, float scale_b,
+                    const float* key_bias,
+                    void* dq_a, void* dk_a, void* dv_a, int64_t ld_da,
+                    void* dq_b, void* dk_b, void* dv_b, int64_t ld_db,
+                    void* workspace, float drop_p, const uint32_t* drop_words, peneo_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * K11 + K12 (+ K13) — handshaking + the pair-classifier heads + class-weighted CE, fused
  * (model/peneo_decoder.py:149-177, 231-292, 315-336, 355-428; model/custom_loss.py:189-202).

@@ -22,7 +22,11 @@
 //     512 contiguous bytes) and zero their fragment afterwards;
 //   * keys past T: K / V rows are clamped to T - 1 and the ragged last tile masks its scores itself; nothing is read from the
 //     padding columns [T, Tp) of key_bias beyond what the clamp allows (index <= T - 1);
-//   * O rows leave as 16-byte pieces straight from the accumulator layout (v_permlane32_swap pairs), no LDS round trip.
+//   * O rows leave as 16-byte pieces straight from the accumulator layout (v_permlane32_swap pairs), no LDS round trip;
+//   * attention dropout (peneo_attn2_fwd_dropout, the DROP instantiation): the keep words of peneo_attn_drop_words arrive as in
+//     attn_fwd_pipe_kernel<true> - every wave's 64 keep-word slots of the tile for ITS 32 queries by one dword DMA (1 KiB more per
+//     buffer), register r's 64-lane mask by two v_readlane, one v_cndmask per element - applied to P after the row sum (lse is the
+//     pre-dropout log-sum-exp), both value streams under the same mask, 1 / (1 - p) once on the accumulators.
 // Nothing here waits on another workgroup.
 #include "common.h"
 
@@ -35,15 +39,17 @@ struct Attn2Params {
   int B, nh, T, Tp; float scale_a, scale_b;
   const float* key_bias;
   void* out_a; int64_t ld_out_a; void* out_b; int64_t ld_out_b; float* lse;
+  float keep_scale; const uint32_t* words; int nqb, Tk;           // dropout keep bits (peneo_attn_drop_words) or NULL
 };
 
 constexpr int DA = 64, DB = 16;   // head dims of the two streams
 constexpr int TK = 32;            // keys per tile
 constexpr int WQ = 128;           // queries per workgroup (4 waves x 32)
 // a tile's buffer: K_a [32][128 B], V_a [32][128 B], K_b [32][32 B], V_b [32][32 B], key bias [64] fp32 (the first 32 are the tile's)
-constexpr int O_KA = 0, O_VA = 4096, O_KB = 8192, O_VB = 9216, O_BIAS = 10240, BUF = 10496;
+// with dropout: + the keep words [4 query blocks][64 slots] (attn_fwd_pipe.hip)
+constexpr int O_KA = 0, O_VA = 4096, O_KB = 8192, O_VB = 9216, O_BIAS = 10240, O_WORDS = 10496;
 constexpr int NBUF = 3;
-constexpr int LDS_BYTES = NBUF * BUF;
+constexpr int buf_bytes(bool drop) { return drop ? O_WORDS + 1024 : O_WORDS; }
 constexpr float kLog2e = 1.4426950408889634f;
 constexpr float kMasked = -1.0e30f;
 constexpr float kRescaleTau = 4.0f;   // (attention.hip: RESCALE_TAU)
@@ -61,6 +67,16 @@ __device__ __forceinline__ void dma4_s(uint32_t voff_lane, const char* base_unif
   asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2\n\ts_mov_b32 m0, %0"
                : "=&s"(keep) : "v"(voff_lane), "s"(base_uniform), "s"(lds_uniform) : "memory");
 }
+// x where the lane's bit of the 64-bit mask is set, else 0 (attention.hip: mask_keep; the s_nop pads the VALU-written-SGPR hazard)
+__device__ __forceinline__ float mask_keep(float x, uint64_t m) {
+  float r;
+  asm("s_nop 1\n\tv_cndmask_b32_e64 %0, 0, %1, %2" : "=v"(r) : "v"(x), "s"(m));
+  return r;
+}
+__device__ __forceinline__ uint64_t lane_words_mask(uint32_t w, int word /* even, compile-time */) {
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)w, word), hi = (uint32_t)__builtin_amdgcn_readlane((int)w, word + 1);
+  return (uint64_t)lo | ((uint64_t)hi << 32);
+}
 // 8 bf16 of a query row, times `scale`, rounded to bf16 again (peneo_head_concat's arithmetic)
 __device__ __forceinline__ uint4 scaled_q(const bf16_t* p, float scale, bool ok) {
   float f[8];
@@ -73,8 +89,10 @@ __device__ __forceinline__ uint4 scaled_q(const bf16_t* p, float scale, bool ok)
   return ok ? v : make_uint4(0u, 0u, 0u, 0u);
 }
 
+template <bool DROP>
 __global__ __launch_bounds__(256, 2) void attn2_fwd_pipe_kernel(Attn2Params p) {
   typedef bf16_t T;
+  constexpr int BUF = buf_bytes(DROP);
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, l31 = lane & 31;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -124,6 +142,8 @@ __global__ __launch_bounds__(256, 2) void attn2_fwd_pipe_kernel(Attn2Params p) {
   const char* nva = reinterpret_cast<const char*>(Va);
   const char* nb = reinterpret_cast<const char*>(wave == 0 ? Kb : Vb);     // (waves 0 and 1 only)
   const char* nkb = reinterpret_cast<const char*>(has_kb ? p.key_bias + (int64_t)b * p.Tp : nullptr);
+  // with dropout every wave also sends the 64 keep-word slots that start at the tile's first key for ITS 32 queries
+  const char* nw = DROP ? reinterpret_cast<const char*>(p.words + ((int64_t)bh * p.nqb + (qb * 4 + wave)) * (int64_t)p.Tk) : nullptr;
   int nk0 = 0;                                       // first key of the next tile to request
   auto dma_tile = [&](auto buf_c) {
     const int buf = buf_c;
@@ -134,6 +154,7 @@ __global__ __launch_bounds__(256, 2) void attn2_fwd_pipe_kernel(Attn2Params p) {
     lds_dma_1k_s<0>(ko, nva, dst + O_VA + wave * 1024);
     if (wave < 2) lds_dma_1k_s<0>((uint32_t)min(brow, last) * ldb2 + bcol, nb, dst + (wave == 0 ? O_KB : O_VB));
     else if (wave == 2 && has_kb) dma4_s((uint32_t)min(nk0 + lane, Tn - 1) * 4u, nkb, dst + O_BIAS);
+    if (DROP) dma4_s((uint32_t)min(nk0 + lane, p.Tk - 1) * 4u, nw, dst + O_WORDS + wave * 256);
     nka += (int64_t)TK * lda2; nva += (int64_t)TK * lda2; nb += (int64_t)TK * ldb2; nk0 += TK;
   };
 
@@ -157,6 +178,7 @@ __global__ __launch_bounds__(256, 2) void attn2_fwd_pipe_kernel(Attn2Params p) {
     aTb[w8] = O_VB + row * 32 + ((li & 3) << 3);
   }
   const int aKb = O_BIAS + 16 * half;                                    // key bias of registers 4 g .. 4 g + 3: + 32 g
+  const int aW = O_WORDS + wave * 256 + lane * 4;                        // lane L: keep word of key slot L of the tile
 
   f32x16_t o[3], s;
 #pragma unroll
@@ -197,6 +219,8 @@ __global__ __launch_bounds__(256, 2) void attn2_fwd_pipe_kernel(Attn2Params p) {
     }
     if (t + 2 < nt) dma_tile(nn);
     const char* buf = smem + cur * BUF;
+    uint32_t cw = 0u;
+    if constexpr (DROP) cw = *reinterpret_cast<const uint32_t*>(buf + aW);
     // scores (natural units) and the block's row maximum  (attention.hip: the `block` lambda of attn_fwd_kernel at scale 1, same order)
     float mt = kMasked;
 #pragma unroll
@@ -234,11 +258,28 @@ __global__ __launch_bounds__(256, 2) void attn2_fwd_pipe_kernel(Attn2Params p) {
     }
     const float nm = -m_run * kLog2e;
     float ls = 0.f;
+    if constexpr (DROP) {                              // (the sum is taken before the mask: lse is the pre-dropout log-sum-exp)
+      auto soft = [&](auto r_c) {
+        constexpr int r = decltype(r_c)::value;
+        const float e = __builtin_amdgcn_exp2f(fmaf(s[r], kLog2e, nm));
+        ls += e;
+        s[r] = mask_keep(e, lane_words_mask(cw, 2 * r));
+      };
+      soft(std::integral_constant<int, 0>{}); soft(std::integral_constant<int, 1>{});
+      soft(std::integral_constant<int, 2>{}); soft(std::integral_constant<int, 3>{});
+      soft(std::integral_constant<int, 4>{}); soft(std::integral_constant<int, 5>{});
+      soft(std::integral_constant<int, 6>{}); soft(std::integral_constant<int, 7>{});
+      soft(std::integral_constant<int, 8>{}); soft(std::integral_constant<int, 9>{});
+      soft(std::integral_constant<int, 10>{}); soft(std::integral_constant<int, 11>{});
+      soft(std::integral_constant<int, 12>{}); soft(std::integral_constant<int, 13>{});
+      soft(std::integral_constant<int, 14>{}); soft(std::integral_constant<int, 15>{});
+    } else {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const float e = __builtin_amdgcn_exp2f(fmaf(s[r], kLog2e, nm));
-      ls += e;
-      s[r] = e;
+      for (int r = 0; r < 16; ++r) {
+        const float e = __builtin_amdgcn_exp2f(fmaf(s[r], kLog2e, nm));
+        ls += e;
+        s[r] = e;
+      }
     }
     ls += __shfl_xor(ls, 32, 64);
     l_run += ls;
@@ -272,7 +313,7 @@ __global__ __launch_bounds__(256, 2) void attn2_fwd_pipe_kernel(Attn2Params p) {
 
   // ---- normalise; O rows: accumulator = [d rows (registers)][query (lane)], two groups + a v_permlane32_swap = 16 bytes per lane ----
   const bool any = m_run > 0.5f * kMasked;
-  const float inv = (any && l_run > 0.f) ? 1.0f / l_run : 0.f;
+  const float inv = (any && l_run > 0.f) ? (DROP ? p.keep_scale : 1.0f) / l_run : 0.f;   // (1 / (1 - p) once, on the accumulators)
   if (half == 0 && myq < Tn && p.lse) p.lse[(int64_t)bh * Tn + myq] = any ? fmaf(m_run, kLog2e, log2f(l_run)) : kMasked;   // log2 units
   // (a row whose keys are all masked: zeros - with the running maximum at -1e30 its P can be inf and its accumulators inf - inf,
   // attention.hip: `any`)
@@ -306,31 +347,52 @@ using namespace peneo;
 
 extern "C" int peneo_attn2_supported(int dtype, int d_a, int d_b) { return dtype == PENEO_BF16 && d_a == DA && d_b == DB ? 1 : 0; }
 
-extern "C" int peneo_attn2_fwd(int dtype, const void* q_a, const void* k_a, const void* v_a, int64_t ld_a, const void* q_b,
-                               const void* k_b, const void* v_b, int64_t ld_b, int B, int nh, int T, int d_a, int d_b, float scale_a,
-                               float scale_b, const float* key_bias, void* out_a, int64_t ld_out_a, void* out_b, int64_t ld_out_b,
-                               float* lse, peneo_stream_t stream) {
-  PENEO_REQUIRE(peneo_attn2_supported(dtype, d_a, d_b), "peneo_attn2_fwd: dtype %d with head dims %d + %d is not supported (bf16, 64 + 16)",
+static int attn2_fwd_launch(const char* who, int dtype, const void* q_a, const void* k_a, const void* v_a, int64_t ld_a, const void* q_b,
+                            const void* k_b, const void* v_b, int64_t ld_b, int B, int nh, int T, int d_a, int d_b, float scale_a,
+                            float scale_b, const float* key_bias, void* out_a, int64_t ld_out_a, void* out_b, int64_t ld_out_b,
+                            float* lse, float drop_p, const uint32_t* drop_words, peneo_stream_t stream) {
+  PENEO_REQUIRE(peneo_attn2_supported(dtype, d_a, d_b), "%s: dtype %d with head dims %d + %d is not supported (bf16, 64 + 16)", who,
                 dtype, d_a, d_b);
-  PENEO_REQUIRE(B > 0 && nh > 0 && T > 0, "peneo_attn2_fwd: bad sizes (B %d, nh %d, T %d)", B, nh, T);
-  PENEO_REQUIRE(q_a && k_a && v_a && q_b && k_b && v_b && out_a && out_b, "peneo_attn2_fwd: null operand or output");
+  PENEO_REQUIRE(B > 0 && nh > 0 && T > 0, "%s: bad sizes (B %d, nh %d, T %d)", who, B, nh, T);
+  PENEO_REQUIRE(q_a && k_a && v_a && q_b && k_b && v_b && out_a && out_b, "%s: null operand or output", who);
   auto al = [](const void* q, uintptr_t m) { return (reinterpret_cast<uintptr_t>(q) & m) == 0; };
   PENEO_REQUIRE(al(q_a, 15) && al(k_a, 15) && al(v_a, 15) && al(q_b, 15) && al(k_b, 15) && al(v_b, 15) && al(out_a, 15) && al(out_b, 15),
-                "peneo_attn2_fwd: operands and outputs must be 16-byte aligned");
-  PENEO_REQUIRE(al(key_bias, 3) && al(lse, 3), "peneo_attn2_fwd: key_bias and lse must be 4-byte aligned");
+                "%s: operands and outputs must be 16-byte aligned", who);
+  PENEO_REQUIRE(al(key_bias, 3) && al(lse, 3), "%s: key_bias and lse must be 4-byte aligned", who);
   PENEO_REQUIRE(ld_a >= (int64_t)nh * DA && ld_out_a >= (int64_t)nh * DA && ld_b >= (int64_t)nh * DB && ld_out_b >= (int64_t)nh * DB,
-                "peneo_attn2_fwd: leading dims too small");
+                "%s: leading dims too small", who);
   PENEO_REQUIRE((ld_a * 2) % 16 == 0 && (ld_b * 2) % 16 == 0 && (ld_out_a * 2) % 16 == 0 && (ld_out_b * 2) % 16 == 0,
-                "peneo_attn2_fwd: row strides must be multiples of 16 bytes");
+                "%s: row strides must be multiples of 16 bytes", who);
   // the kernel's per-lane DMA offsets (a key row of a tile, a key-bias index) are 32-bit byte offsets
   PENEO_REQUIRE(ld_a * 2 * TK < (1ll << 31) && ld_b * 2 * TK < (1ll << 31) && (int64_t)T * 4 < (1ll << 31),
-                "peneo_attn2_fwd: row strides or T beyond the kernel's 32-bit lane offsets");
+                "%s: row strides or T beyond the kernel's 32-bit lane offsets", who);
+  PENEO_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "%s: drop_p out of range", who);
+  PENEO_REQUIRE(drop_p == 0.f || (drop_words && al(drop_words, 3)), "%s: drop_p > 0 needs the keep words of peneo_attn_drop_words", who);
   const int64_t units = (int64_t)((T + WQ - 1) / WQ) * nh * B;
-  PENEO_REQUIRE(units < (1ll << 31), "peneo_attn2_fwd: too many workgroups");
+  PENEO_REQUIRE(units < (1ll << 31), "%s: too many workgroups", who);
   Attn2Params p = {};
   p.q_a = q_a; p.k_a = k_a; p.v_a = v_a; p.ld_a = ld_a; p.q_b = q_b; p.k_b = k_b; p.v_b = v_b; p.ld_b = ld_b;
   p.B = B; p.nh = nh; p.T = T; p.Tp = peneo_attn_padded_len(T); p.scale_a = scale_a; p.scale_b = scale_b; p.key_bias = key_bias;
   p.out_a = out_a; p.ld_out_a = ld_out_a; p.out_b = out_b; p.ld_out_b = ld_out_b; p.lse = lse;
-  hipLaunchKernelGGL(attn2_fwd_pipe_kernel, dim3((unsigned)units), dim3(256), LDS_BYTES, (hipStream_t)stream, p);
-  return check_launch("peneo_attn2_fwd");
+  p.keep_scale = pair_drop_scale_host(drop_p); p.words = drop_words;
+  peneo_attn_drop_words_dims(T, &p.nqb, &p.Tk);
+  if (drop_p > 0.f) hipLaunchKernelGGL(attn2_fwd_pipe_kernel<true>, dim3((unsigned)units), dim3(256), NBUF * buf_bytes(true), (hipStream_t)stream, p);
+  else hipLaunchKernelGGL(attn2_fwd_pipe_kernel<false>, dim3((unsigned)units), dim3(256), NBUF * buf_bytes(false), (hipStream_t)stream, p);
+  return check_launch(who);
+}
+
+extern "C" int peneo_attn2_fwd(int dtype, const void* q_a, const void* k_a, const void* v_a, int64_t ld_a, const void* q_b,
+                               const void* k_b, const void* v_b, int64_t ld_b, int B, int nh, int T, int d_a, int d_b, float scale_a,
+                               float scale_b, const float* key_bias, void* out_a, int64_t ld_out_a, void* out_b, int64_t ld_out_b,
+                               float* lse, peneo_stream_t stream) {
+  return attn2_fwd_launch("peneo_attn2_fwd", dtype, q_a, k_a, v_a, ld_a, q_b, k_b, v_b, ld_b, B, nh, T, d_a, d_b, scale_a, scale_b, key_bias,
+                          out_a, ld_out_a, out_b, ld_out_b, lse, 0.f, nullptr, stream);
+}
+
+extern "C" int peneo_attn2_fwd_dropout(int dtype, const void* q_a, const void* k_a, const void* v_a, int64_t ld_a, const void* q_b,
+                                       const void* k_b, const void* v_b, int64_t ld_b, int B, int nh, int T, int d_a, int d_b,
+                                       float scale_a, float scale_b, const float* key_bias, void* out_a, int64_t ld_out_a, void* out_b,
+                                       int64_t ld_out_b, float* lse, float drop_p, const uint32_t* drop_words, peneo_stream_t stream) {
+  return attn2_fwd_launch("peneo_attn2_fwd_dropout", dtype, q_a, k_a, v_a, ld_a, q_b, k_b, v_b, ld_b, B, nh, T, d_a, d_b, scale_a, scale_b,
+                          key_bias, out_a, ld_out_a, out_b, ld_out_b, lse, drop_p, drop_words, stream);
 }

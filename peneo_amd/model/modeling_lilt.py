@@ -155,6 +155,7 @@ class _State:
         self.dtype = torch.float32
         self.dims = None
         self.attn2 = False        # this forward's attention runs as the two-stream kernel (_use_attn2)
+        self.attn2_train = False  # ... as the two-stream forward with dropout + the two-stream backward (_use_attn2_train)
 
 
 class _LiltEmbedStage(torch.autograd.Function):
@@ -326,6 +327,14 @@ def _use_attn2(dt, seeds, d, dl) -> bool:
             and os.environ.get("PENEO_LILT_ATTN2", "1") != "0")
 
 
+def _use_attn2_train(dt, seeds, d, dl) -> bool:
+    """The two-stream attention for TRAINING forwards (autograd enabled or attention dropout active): ops.attn2_fwd with the
+    layer's keep words and ops.attn2_bwd instead of the concat path - no `cat`, no `attc`, no packed gradient copies.  Opt-in:
+    PENEO_LILT_ATTN2_TRAIN=1, read at call time; off by default.  Bit-identical to the path it replaces (tests/test_gpu_attn2_bwd.py)."""
+    return (dt == torch.bfloat16 and (torch.is_grad_enabled() or seeds.p_attn > 0.0) and ops.attn2_supported(dt, d, dl)
+            and os.environ.get("PENEO_LILT_ATTN2_TRAIN", "0") == "1")
+
+
 class _LiltLayerStage(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, st, idx, x, l, *params):
@@ -364,6 +373,23 @@ class _LiltLayerStage(torch.autograd.Function):
                 xo, _ = _post_attn_fwd(wc, f"L{idx}.t", dt, cfg.layer_norm_eps, seeds, site + 2, x, att, tp)
                 lo, _ = _post_attn_fwd(wc, f"L{idx}.l", dt, cfg.layer_norm_eps, seeds, site + 6, l, latt, lp)
             return xo, lo
+        if st.attn2_train:
+            # the training form of the above: the same kernel with the layer's keep words; the backward reads qkv / lqkv in place
+            att = torch.empty((R, H), dtype=dt, device=dev)
+            latt = torch.empty((R, Hl), dtype=dt, device=dev)
+            _, _, lse = ops.attn2_fwd(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], lqkv[:, :Hl], lqkv[:, Hl:2 * Hl], lqkv[:, 2 * Hl:],
+                                      B, nh, S, 1.0 / math.sqrt(d), 1.0 / math.sqrt(dl), st.key_bias, out_a=att, out_b=latt,
+                                      drop_p=seeds.p_attn, drop_words=seeds.attn_words(idx, cfg.num_hidden_layers, B, nh, S, dev))
+            if grouped:
+                xo, lo, sv_t, sv_l = _post_attn_fwd2(wc, idx, dt, cfg.layer_norm_eps, seeds, site + 2, site + 6, x, att, tp, l, latt, lp)
+            else:
+                xo, sv_t = _post_attn_fwd(wc, f"L{idx}.t", dt, cfg.layer_norm_eps, seeds, site + 2, x, att, tp)
+                lo, sv_l = _post_attn_fwd(wc, f"L{idx}.l", dt, cfg.layer_norm_eps, seeds, site + 6, l, latt, lp)
+            ctx.grouped = grouped
+            ctx.model, ctx.st, ctx.idx = model, st, idx
+            ctx.saved = (x, l, qkv, lqkv, lse, sv_t, sv_l)     # (att / latt are sv_t[0] / sv_l[0])
+            ctx.params = params
+            return xo, lo
         cat = torch.empty((R, 3 * nh * dc), dtype=dt, device=dev)
         ops.head_concat(qkv[:, :H], lqkv[:, :Hl], nh, cat[:, :nh * dc], 1.0 / math.sqrt(d), 1.0 / math.sqrt(dl))
         ops.head_concat(qkv[:, H:], lqkv[:, Hl:], 2 * nh, cat[:, nh * dc:])      # k and v in one launch: 2 nh "heads"
@@ -389,7 +415,7 @@ class _LiltLayerStage(torch.autograd.Function):
         model, st, idx = ctx.model, ctx.st, ctx.idx
         (wq, bq, wk, bk, wv, bv, lwq, lbq, lwk, lbk, lwv, lbv, *rest) = ctx.params
         tp, lp = rest[:10], rest[10:]
-        x, l, cat, attc, lse, sv_t, sv_l = ctx.saved
+        x, l, cat, attc, lse, sv_t, sv_l = ctx.saved       # (st.attn2_train: qkv and lqkv where the concat path keeps cat and attc)
         cfg, wc, dt = model.config, model.weight_cache, st.dtype
         B, S = st.dims
         H, nh = cfg.hidden_size, cfg.num_attention_heads
@@ -423,16 +449,23 @@ class _LiltLayerStage(torch.autograd.Function):
         else:
             d_att, d_x_res, gt = _post_attn_bwd(wc, f"L{idx}.t", dt, seeds, site + 2, d_xo, sv_t, tp, on_side)
             d_latt, d_l_res, gl = _post_attn_bwd(wc, f"L{idx}.l", dt, seeds, site + 6, d_lo, sv_l, lp, on_side)
-        d_attc = torch.empty((R, nh * dc), dtype=dt, device=dev)
-        ops.head_concat(d_att, d_latt, nh, d_attc)
-        qc, kc, vc = cat[:, :nh * dc], cat[:, nh * dc:2 * nh * dc], cat[:, 2 * nh * dc:]
-        dcat = torch.empty_like(cat)
-        ops.attn_bwd(qc, kc, vc, attc, d_attc, lse, B, nh, S, dc, 1.0, None, st.key_bias, dcat, None, drop_p=seeds.p_attn,
-                     drop_words=seeds.attn_words(idx, cfg.num_hidden_layers, B, nh, S, dcat.device))
         dqkv = torch.empty((R, 3 * H), dtype=dt, device=dev)
         dlqkv = torch.empty((R, 3 * Hl), dtype=dt, device=dev)
-        ops.head_split(dcat[:, :nh * dc], nh, dqkv[:, :H], dlqkv[:, :Hl], 1.0 / math.sqrt(d), 1.0 / math.sqrt(dl))
-        ops.head_split(dcat[:, nh * dc:], 2 * nh, dqkv[:, H:], dlqkv[:, Hl:])
+        if st.attn2_train:
+            qkv, lqkv = cat, attc
+            ops.attn2_bwd(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], lqkv[:, :Hl], lqkv[:, Hl:2 * Hl], lqkv[:, 2 * Hl:],
+                          sv_t[0], d_att, sv_l[0], d_latt, lse, B, nh, S, 1.0 / math.sqrt(d), 1.0 / math.sqrt(dl), st.key_bias,
+                          dqkv, dlqkv, drop_p=seeds.p_attn,
+                          drop_words=seeds.attn_words(idx, cfg.num_hidden_layers, B, nh, S, dev))
+        else:
+            d_attc = torch.empty((R, nh * dc), dtype=dt, device=dev)
+            ops.head_concat(d_att, d_latt, nh, d_attc)
+            qc, kc, vc = cat[:, :nh * dc], cat[:, nh * dc:2 * nh * dc], cat[:, 2 * nh * dc:]
+            dcat = torch.empty_like(cat)
+            ops.attn_bwd(qc, kc, vc, attc, d_attc, lse, B, nh, S, dc, 1.0, None, st.key_bias, dcat, None, drop_p=seeds.p_attn,
+                         drop_words=seeds.attn_words(idx, cfg.num_hidden_layers, B, nh, S, dcat.device))
+            ops.head_split(dcat[:, :nh * dc], nh, dqkv[:, :H], dlqkv[:, :Hl], 1.0 / math.sqrt(d), 1.0 / math.sqrt(dl))
+            ops.head_split(dcat[:, nh * dc:], 2 * nh, dqkv[:, H:], dlqkv[:, Hl:])
         Wqkv = wc.cat_rows(f"L{idx}.qkv", [wq, wk, wv], dt)
         Wlqkv = wc.cat_rows(f"L{idx}.lqkv", [lwq, lwk, lwv], dt)
         wg = lambda dy, xin: ops.gemm(dy, xin, a_kmajor=False, b_kmajor=False, out_dtype=torch.float32)
@@ -570,6 +603,7 @@ class LiltModel(nn.Module):
         st.key_bias = kb
         H, nh = cfg.hidden_size, cfg.num_attention_heads
         st.attn2 = _use_attn2(st.dtype, st.seeds, H // nh, H // cfg.channel_shrink_ratio // nh)   # once per forward; the layers follow
+        st.attn2_train = _use_attn2_train(st.dtype, st.seeds, H // nh, H // cfg.channel_shrink_ratio // nh)
         e, le = self.embeddings, self.layout_embeddings
         eparams = [e.word_embeddings.weight, e.token_type_embeddings.weight, e.position_embeddings.weight,
                    e.LayerNorm.weight, e.LayerNorm.bias, le.x_position_embeddings.weight, le.y_position_embeddings.weight,

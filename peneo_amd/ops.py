@@ -553,11 +553,14 @@ def attn2_supported(dtype: torch.dtype, d_a: int, d_b: int) -> bool:
 
 def attn2_fwd(q_a: torch.Tensor, k_a: torch.Tensor, v_a: torch.Tensor, q_b: torch.Tensor, k_b: torch.Tensor, v_b: torch.Tensor,
               B: int, nh: int, T: int, scale_a: float, scale_b: float, key_bias: Optional[torch.Tensor] = None,
-              out_a: Optional[torch.Tensor] = None, out_b: Optional[torch.Tensor] = None, lse: Optional[torch.Tensor] = None):
+              out_a: Optional[torch.Tensor] = None, out_b: Optional[torch.Tensor] = None, lse: Optional[torch.Tensor] = None,
+              drop_p: float = 0.0, drop_words: Optional[torch.Tensor] = None):
     """Two-stream attention forward (LiLT): scores = (scale_a q_a).k_a + (scale_b q_b).k_b + key_bias, one softmax,
     out_a = P v_a and out_b = P v_b.  q_a/k_a/v_a: 2-D views [B*T, nh*d_a] with a common row stride, q_b/k_b/v_b: [B*T, nh*d_b]
     likewise (e.g. column slices of the fused qkv and lqkv buffers); key_bias: fp32 [B, Tp] additive (0 / -1e30).
     out_a [B*T, nh*d_a], out_b [B*T, nh*d_b] (row strides may be larger) and lse [B, nh, T] may be given.
+    Attention dropout: `drop_p` with `drop_words` = one set of attn_drop_words (both value streams share the mask; attn2_bwd takes
+    the same set); with both unset the call is peneo_attn2_fwd, otherwise peneo_attn2_fwd_dropout.
     Returns (out_a, out_b, lse); equal bit for bit to head_concat x 2 -> attn_fwd(d_a + d_b, scale 1) -> head_split."""
     assert q_a.dim() == 2 and q_b.dim() == 2 and q_a.shape[0] == q_b.shape[0] == B * T
     assert q_a.dtype == k_a.dtype == v_a.dtype == q_b.dtype == k_b.dtype == v_b.dtype
@@ -577,10 +580,63 @@ def attn2_fwd(q_a: torch.Tensor, k_a: torch.Tensor, v_a: torch.Tensor, q_b: torc
     assert lse.is_contiguous() and lse.shape == (B, nh, T) and lse.dtype == torch.float32
     if key_bias is not None:
         assert key_bias.dtype == torch.float32 and key_bias.is_contiguous() and key_bias.shape == (B, attn_padded_len(T))
-    check(lib().peneo_attn2_fwd(dtype_code(q_a.dtype), ptr(q_a), ptr(k_a), ptr(v_a), q_a.stride(0), ptr(q_b), ptr(k_b), ptr(v_b),
-                                q_b.stride(0), B, nh, T, d_a, d_b, scale_a, scale_b, ptr(key_bias), ptr(out_a), out_a.stride(0),
-                                ptr(out_b), out_b.stride(0), ptr(lse), stream()), "peneo_attn2_fwd")
+    if drop_p == 0.0 and drop_words is None:
+        check(lib().peneo_attn2_fwd(dtype_code(q_a.dtype), ptr(q_a), ptr(k_a), ptr(v_a), q_a.stride(0), ptr(q_b), ptr(k_b), ptr(v_b),
+                                    q_b.stride(0), B, nh, T, d_a, d_b, scale_a, scale_b, ptr(key_bias), ptr(out_a), out_a.stride(0),
+                                    ptr(out_b), out_b.stride(0), ptr(lse), stream()), "peneo_attn2_fwd")
+        return out_a, out_b, lse
+    _check_drop_words(drop_words, B, nh, T)
+    check(lib().peneo_attn2_fwd_dropout(dtype_code(q_a.dtype), ptr(q_a), ptr(k_a), ptr(v_a), q_a.stride(0), ptr(q_b), ptr(k_b),
+                                        ptr(v_b), q_b.stride(0), B, nh, T, d_a, d_b, scale_a, scale_b, ptr(key_bias), ptr(out_a),
+                                        out_a.stride(0), ptr(out_b), out_b.stride(0), ptr(lse), drop_p,
+                                        ptr(drop_words) if drop_p > 0 else None, stream()), "peneo_attn2_fwd_dropout")
     return out_a, out_b, lse
+
+
+def _check_drop_words(drop_words: Optional[torch.Tensor], B: int, nh: int, T: int) -> None:
+    if drop_words is not None:
+        assert drop_words.dtype == torch.int32 and drop_words.is_contiguous()
+        assert tuple(drop_words.shape) == attn_drop_words_shape(B, nh, T)[1:], "one set of attn_drop_words for (B, nh, T)"
+
+
+def attn2_bwd_workspace_bytes(B: int, nh: int, T: int) -> int:
+    return int(lib().peneo_attn2_bwd_workspace_bytes(B, nh, T))
+
+
+def attn2_bwd(q_a: torch.Tensor, k_a: torch.Tensor, v_a: torch.Tensor, q_b: torch.Tensor, k_b: torch.Tensor, v_b: torch.Tensor,
+              out_a: torch.Tensor, d_out_a: torch.Tensor, out_b: torch.Tensor, d_out_b: torch.Tensor, lse: torch.Tensor,
+              B: int, nh: int, T: int, scale_a: float, scale_b: float, key_bias: Optional[torch.Tensor],
+              dqkv_a: torch.Tensor, dqkv_b: torch.Tensor, drop_p: float = 0.0, drop_words: Optional[torch.Tensor] = None):
+    """Two-stream attention backward (LiLT): the gradients of attn2_fwd's contract with respect to the unscaled q | k | v of both
+    streams, written as dq | dk | dv into dqkv_a [B*T, 3*nh*d_a] and dqkv_b [B*T, 3*nh*d_b] (the fused-QKV layout; row strides may
+    be larger).  out_* / lse: what attn2_fwd returned; d_out_*: their gradients (out_a / d_out_a share a row stride, out_b /
+    d_out_b likewise); drop_p / drop_words: what the forward took.  The workspace (delta and the dS^T slab) is allocated here from
+    peneo_attn2_bwd_workspace_bytes.  Equal bit for bit to head_concat -> attn_bwd(d_a + d_b, scale 1) -> head_split x 2."""
+    assert q_a.dim() == 2 and q_b.dim() == 2 and q_a.shape[0] == q_b.shape[0] == B * T
+    assert q_a.dtype == k_a.dtype == v_a.dtype == q_b.dtype == k_b.dtype == v_b.dtype
+    assert q_a.stride(0) == k_a.stride(0) == v_a.stride(0) and q_a.stride(1) == k_a.stride(1) == v_a.stride(1) == 1
+    assert q_b.stride(0) == k_b.stride(0) == v_b.stride(0) and q_b.stride(1) == k_b.stride(1) == v_b.stride(1) == 1
+    assert q_a.shape == k_a.shape == v_a.shape and q_b.shape == k_b.shape == v_b.shape
+    assert q_a.shape[1] % nh == 0 and q_b.shape[1] % nh == 0
+    Ha, Hb = q_a.shape[1], q_b.shape[1]
+    d_a, d_b = Ha // nh, Hb // nh
+    for o, g, w in ((out_a, d_out_a, Ha), (out_b, d_out_b, Hb)):
+        assert o.shape == g.shape == (B * T, w) and o.dtype == g.dtype == q_a.dtype
+        assert o.stride(0) == g.stride(0) and o.stride(1) == g.stride(1) == 1
+    assert lse.is_contiguous() and lse.shape == (B, nh, T) and lse.dtype == torch.float32
+    assert dqkv_a.shape == (B * T, 3 * Ha) and dqkv_a.stride(1) == 1 and dqkv_a.dtype == q_a.dtype
+    assert dqkv_b.shape == (B * T, 3 * Hb) and dqkv_b.stride(1) == 1 and dqkv_b.dtype == q_a.dtype
+    if key_bias is not None:
+        assert key_bias.dtype == torch.float32 and key_bias.is_contiguous() and key_bias.shape == (B, attn_padded_len(T))
+    _check_drop_words(drop_words, B, nh, T)
+    ws = torch.empty(max(attn2_bwd_workspace_bytes(B, nh, T), 16), dtype=torch.uint8, device=q_a.device)
+    check(lib().peneo_attn2_bwd(dtype_code(q_a.dtype), ptr(q_a), ptr(k_a), ptr(v_a), q_a.stride(0), ptr(q_b), ptr(k_b), ptr(v_b),
+                                q_b.stride(0), ptr(out_a), ptr(d_out_a), out_a.stride(0), ptr(out_b), ptr(d_out_b), out_b.stride(0),
+                                ptr(lse), B, nh, T, d_a, d_b, scale_a, scale_b, ptr(key_bias), ptr(dqkv_a[:, :Ha]),
+                                ptr(dqkv_a[:, Ha:2 * Ha]), ptr(dqkv_a[:, 2 * Ha:]), dqkv_a.stride(0), ptr(dqkv_b[:, :Hb]),
+                                ptr(dqkv_b[:, Hb:2 * Hb]), ptr(dqkv_b[:, 2 * Hb:]), dqkv_b.stride(0), ptr(ws), drop_p,
+                                ptr(drop_words) if drop_p > 0 else None, stream()), "peneo_attn2_bwd")
+    return dqkv_a, dqkv_b
 
 
 def attn_bwd(q, k, v, out, d_out, lse, B: int, nh: int, T: int, d: int, scale: float, bias, key_bias,
