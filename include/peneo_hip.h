@@ -460,6 +460,30 @@ int peneo_pair_heads_fwd_mxfp8(const void* ab, int B, int N, const peneo_pair_he
                                float* const* logits /* host array of num_heads device pointers, or NULL */,
                                const peneo_pair_loss* loss, peneo_stream_t stream);
 
+/* MXFP8 train forward of the same heads (version 105): the first layer of peneo_pair_heads_fwd_mxfp8 - same quantizer, same scaled
+ * MFMAs in the same order - on the walk of peneo_pair_heads_fwd_save, leaving what peneo_pair_bwd_saved reads.
+ * peneo_pair_mxfp8_save_supported: host-side query (no GPU call): 1 exactly when peneo_pair_save_supported(PENEO_BF16, D, num_heads)
+ * and peneo_pair_mxfp8_supported(D, num_heads) are both 1 (D = 384), else 0.
+ * peneo_pair_heads_fwd_mxfp8_save: ab [B, N, 2D] bf16; `desc` as for peneo_pair_heads_fwd with w_packed from
+ * peneo_pair_heads_pack_mxfp8 and drop_p in [0, 1); act / x_rows as for peneo_pair_heads_fwd_save (both required, 16-byte aligned);
+ * `loss` (may be NULL) may carry dlogits; `loss->partials` has peneo_pair_loss_partials_save(B, N) rows.  Per pair:
+ *   x = SiLU(a_i + b_j) in fp32; x_rows receives bf16(x), the bytes peneo_pair_heads_fwd_save writes;
+ *   z = Q(W1) Q(x) + b1, Q the MXFP8 quantizer above (with drop_p = 0 the logits are those of peneo_pair_heads_fwd_mxfp8 bit for bit);
+ *   the K12 dropout mask of (drop_seed, drop_p) is the one the bf16 forwards draw; the record holds f16(z) of a kept unit and
+ *   -30000 of a dropped one, in the layout of peneo_pair_heads_fwd_save; y = bf16(SiLU(z)), 0 where dropped;
+ *   logits = s (W2 y) + b2, s = 65536 / (65536 - round(drop_p 2^16)); loss rows and dlogits as peneo_pair_heads_fwd defines them.
+ * Pairs of a block outside the triangle compute finite values that nobody reads; nothing is written for the absent second block of
+ * the last workgroup.  The RANGE note of peneo_pair_heads_fwd_save applies (|z| < 30000).
+ * GRADIENT: peneo_pair_bwd_saved on these buffers gives straight-through gradients: du = dz W1 and dW1 = dz^T x use the bf16 weights
+ * and the bf16 x, while SiLU' and the loss are taken at this forward's quantized z.
+ * Other arguments give PENEO_ERR_INVALID: an unsupported (D, num_heads), a NULL act / x_rows, a misaligned buffer, drop_p outside
+ * [0, 1).  A w_packed that came from peneo_pair_heads_pack (the bf16 pack) is NOT detectable: the call takes a pointer without a
+ * size; its slabs would be read at the MXFP8 stride (in bounds: the bf16 pack is the larger one) and give meaningless logits. */
+int peneo_pair_mxfp8_save_supported(int D, int num_heads);
+int peneo_pair_heads_fwd_mxfp8_save(const void* ab, int B, int N, const peneo_pair_heads_desc* desc,
+                                    float* const* logits /* host array of num_heads device pointers, or NULL */,
+                                    const peneo_pair_loss* loss, void* act, void* x_rows, peneo_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Block-scaled (OCP MX v1.0) FP8 GEMM:  C[m, n] = epilogue( sum_k A^(m, k) * B^(n, k) ),  x^ = e4m3 element * 2^(E8M0 byte - 127)
  * Both operands are k-major, as every forward nn.Linear (y = x W^T): A_q [M, K] e4m3 bytes with A_s [M, K / 32] E8M0 bytes, B_q [N, K]

@@ -180,6 +180,8 @@ SIGNATURES = {
     "peneo_pair_heads_mxfp8_packed_bytes": (_sz, [_i, _i]),
     "peneo_pair_heads_pack_mxfp8": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
     "peneo_pair_heads_fwd_mxfp8": (_i, [_vp, _i, _i, C.POINTER(PairHeadsDesc), _vp, C.POINTER(PairLoss), _vp]),
+    "peneo_pair_mxfp8_save_supported": (_i, [_i, _i]),
+    "peneo_pair_heads_fwd_mxfp8_save": (_i, [_vp, _i, _i, C.POINTER(PairHeadsDesc), _vp, C.POINTER(PairLoss), _vp, _vp, _vp]),
     "peneo_pair_bwd_saved": (_i, [_i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "peneo_ohem_workspace_bytes": (_sz, [_i64]),
     "peneo_ohem_ce": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -184,6 +184,14 @@ class PEneoModel(PEneoPreTrainedModel):
         self.peneo_decoder.set_pair_heads_format(fmt)
         return self
 
+    def set_pair_heads_train_format(self, fmt: str) -> "PEneoModel":
+        """"bf16" (default) or "mxfp8": the MXFP8 train forward of the five pair classifiers (PEneoDecoder.set_pair_heads_train_format):
+        forwards that need gradients run the classifiers' first layer on block-scaled e4m3 and feed the unchanged saved backward
+        (straight-through gradients).  Independent of set_pair_heads_format, which still refuses gradients.  "mxfp8" needs compute
+        dtype torch.bfloat16, 2-layer classifiers, decoder width 384 and the saved backward switched on; otherwise ValueError."""
+        self.peneo_decoder.set_pair_heads_train_format(fmt, self._compute_dtype)
+        return self
+
     def set_encoder_format(self, fmt: str) -> "PEneoModel":
         """"bf16" (default) or "mxfp8": the MXFP8 inference path of the backbone's encoder layers (LayoutLMv3Model.set_encoder_format;
         eval forwards without gradients only).  Independent of set_pair_heads_format.  "mxfp8" needs compute dtype torch.bfloat16 and

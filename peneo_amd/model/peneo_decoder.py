@@ -250,8 +250,6 @@ class _DecoderStage(torch.autograd.Function):
             res = ops.pair_heads_fwd_mxfp8(ab, wpm, b1cat, b2cat, HEAD_CLASSES, want_logits=want_logits, tags=tags,
                                            class_weights=cws)
             return _DecoderStage._finish(ctx, dec, saved, params, res, tags, cws, ab, B, N, D, seq, dev)
-        wp = wc.get(("dec.pack", dt), w1s + w2s, lambda: ops.pair_heads_pack(dt, [w.detach() for w in w1s],
-                                                                             [w.detach() for w in w2s]))
         # the Dropout between the two layers of every classifier (reference :261) acts on the [B, P, 5D] hidden inside the
         # kernel; the backward regenerates the mask from (p, seed)
         saved["k12_drop"] = (seeds.p_hidden, seeds.seed(903))
@@ -276,6 +274,17 @@ class _DecoderStage(torch.autograd.Function):
             except torch.cuda.OutOfMemoryError:
                 big_clear(dev)
                 save = False
+        if save and dec.pair_heads_train_format == "mxfp8":
+            # opt-in MXFP8 train forward (set_pair_heads_train_format): the first layer on block-scaled e4m3, the same mask and the same
+            # saved buffers; the backward below is unchanged, so its gradients are straight-through on the bf16 weights
+            wpm = wc.get(("dec.pack_mxfp8",), w1s + w2s, lambda: ops.pair_heads_pack_mxfp8([w.detach() for w in w1s],
+                                                                                         [w.detach() for w in w2s]))
+            res = ops.pair_heads_fwd_mxfp8_save(ab, wpm, b1cat, b2cat, HEAD_CLASSES, want_logits=want_logits, tags=tags,
+                                                class_weights=cws, want_dlogits=True, drop_p=seeds.p_hidden,
+                                                drop_seed=seeds.seed(903), save_buffers=bufs)
+            return _DecoderStage._finish(ctx, dec, saved, params, res, tags, cws, ab, B, N, D, seq, dev)
+        wp = wc.get(("dec.pack", dt), w1s + w2s, lambda: ops.pair_heads_pack(dt, [w.detach() for w in w1s],
+                                                                             [w.detach() for w in w2s]))
         res = ops.pair_heads_fwd(ab, wp, b1cat, b2cat, HEAD_CLASSES, want_logits=want_logits,
                                  tags=tags, class_weights=cws, want_dlogits=need_grad and tags is not None,
                                  drop_p=seeds.p_hidden, drop_seed=seeds.seed(903), save=save, save_buffers=bufs)
@@ -670,6 +679,7 @@ class PEneoDecoder(nn.Module):
             raise ValueError(f"decoder hidden size {D} must be a multiple of 32 for the MFMA pair-heads kernel")
         self.decoder_hidden_size = D
         self.pair_heads_format = "bf16"   # set_pair_heads_format
+        self.pair_heads_train_format = "bf16"   # set_pair_heads_train_format
         self.handshaking_kernel = HandshakingKernel(D)
         self.inference_mode = config.inference_mode
 
@@ -726,6 +736,26 @@ class PEneoDecoder(nn.Module):
             if not ops.pair_mxfp8_supported(self.decoder_hidden_size, len(HEAD_NAMES)):
                 raise ValueError(f"mxfp8 pair heads do not support decoder width D = {self.decoder_hidden_size}")
         self.pair_heads_format = fmt
+
+    def set_pair_heads_train_format(self, fmt: str, compute_dtype: torch.dtype = torch.bfloat16) -> None:
+        """"bf16" (default): forwards with gradients run the pair heads in the compute dtype.  "mxfp8": a forward that needs
+        gradients and would save its activations for the fused backward (pair_heads_fwd(save=True)) runs the first layer of the
+        five classifiers on block-scaled e4m3 instead (peneo_pair_heads_fwd_mxfp8_save); the backward is unchanged, so the
+        gradients are straight-through on the bf16 weights, taken at the forward's quantized z.  Independent of
+        set_pair_heads_format (forwards without gradients).  Needs bf16 compute, the 2-layer classifiers, a width both the saved
+        backward and the MXFP8 kernel hold, and the saved backward switched on (save_pair_act / fused_bwd)."""
+        if fmt not in ("bf16", "mxfp8"):
+            raise ValueError(f"unknown pair-heads train format {fmt!r} (expected 'bf16' or 'mxfp8')")
+        if fmt == "mxfp8":
+            if compute_dtype != torch.bfloat16:
+                raise ValueError("the mxfp8 train format of the pair heads needs compute dtype torch.bfloat16")
+            if self.num_cls_layers != 2:
+                raise ValueError(f"the mxfp8 train format of the pair heads needs peneo_classifier_num_layers == 2, not {self.num_cls_layers}")
+            if not ops.pair_mxfp8_save_supported(self.decoder_hidden_size, len(HEAD_NAMES)):
+                raise ValueError(f"the mxfp8 train format of the pair heads does not support decoder width D = {self.decoder_hidden_size}")
+            if not (self.save_pair_act and self.fused_bwd):
+                raise ValueError("the mxfp8 train format of the pair heads feeds the saved backward: save_pair_act and fused_bwd must be on")
+        self.pair_heads_train_format = fmt
 
     def stacked_combine_weight(self, wc_w: torch.Tensor, dt: torch.dtype) -> torch.Tensor:
         """[Wc[:, :D]; Wc[:, D:]] as a [2D, D] working-precision matrix, so one GEMM yields [a | b]."""
@@ -794,6 +824,12 @@ class PEneoDecoder(nn.Module):
                                  "with set_pair_heads_format('bf16')")
             if sequence_output.dtype != torch.bfloat16:
                 raise ValueError("mxfp8 pair heads need compute dtype torch.bfloat16")
+        if self.pair_heads_train_format == "mxfp8" and need_grad:
+            # what set_pair_heads_train_format checked may have been changed since
+            if sequence_output.dtype != torch.bfloat16:
+                raise ValueError("the mxfp8 train format of the pair heads needs compute dtype torch.bfloat16")
+            if not (self.save_pair_act and self.fused_bwd):
+                raise ValueError("the mxfp8 train format of the pair heads feeds the saved backward: save_pair_act and fused_bwd must be on")
         res = _DecoderStage.apply(self, sequence_output.reshape(B * N, Hin), B, N, tags, want_logits, need_grad, *params)
         loss, l_le, l_elh, l_elt, l_lgh, l_lgt, o_le, o_elh, o_elt, o_lgh, o_lgt = res
         if self.inference_mode:

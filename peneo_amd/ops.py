@@ -916,6 +916,65 @@ def pair_heads_fwd_mxfp8(ab: torch.Tensor, wp: torch.Tensor, b1: torch.Tensor, b
     return logits, partials, None
 
 
+def pair_mxfp8_save_supported(D: int, num_heads: int) -> bool:
+    """True when pair_heads_fwd_mxfp8_save exists for this shape: the saved backward and the MXFP8 kernel both hold it (D = 384)."""
+    return bool(lib().peneo_pair_mxfp8_save_supported(int(D), int(num_heads)))
+
+
+def pair_heads_fwd_mxfp8_save(ab: torch.Tensor, wp: torch.Tensor, b1: torch.Tensor, b2: torch.Tensor,
+                              classes: Sequence[int], *, want_logits: bool = True, tags: Optional[Sequence[torch.Tensor]] = None,
+                              class_weights: Optional[Sequence[Optional[torch.Tensor]]] = None, want_dlogits: bool = False,
+                              drop_p: float = 0.0, drop_seed: int = 0, save_buffers=None):
+    """MXFP8 train forward: pair_heads_fwd(save=True) with the first layer of pair_heads_fwd_mxfp8.  ab [B, N, 2D] bf16, wp from
+    pair_heads_pack_mxfp8.  Returns (logits list | None, loss partials [n, 32] | None, dlogits list | None, (act, x_rows)); act and
+    x_rows feed pair_bwd_saved, whose gradients are then straight-through on the quantizer (include/peneo_hip.h)."""
+    _c(ab)
+    assert ab.dtype == torch.bfloat16, "pair_heads_fwd_mxfp8_save takes bf16 ab"
+    B, N, D2 = ab.shape
+    D = D2 // 2
+    P = N * (N + 1) // 2
+    nh = len(classes)
+    if not pair_mxfp8_save_supported(D, nh):
+        raise ValueError(f"MXFP8 train forward of the pair heads: D={D} with {nh} heads is not supported")
+    # the C entry point takes a pointer without a size: a bf16 pack (twice the bytes) is caught here
+    if wp.dtype != torch.uint8 or wp.numel() != lib().peneo_pair_heads_mxfp8_packed_bytes(nh, D):
+        raise ValueError("pair_heads_fwd_mxfp8_save: wp is not a pair_heads_pack_mxfp8 buffer for this shape")
+    desc = hip.PairHeadsDesc()
+    desc.num_heads, desc.D = nh, D
+    for h, c in enumerate(classes):
+        desc.classes[h] = c
+    desc.w_packed, desc.b1, desc.b2 = ptr(wp), ptr(b1), ptr(b2)
+    desc.drop_p, desc.drop_seed = float(drop_p), int(drop_seed) & 0xFFFFFFFF
+    logits = [torch.empty((B, P, c), dtype=torch.float32, device=ab.device) for c in classes] if want_logits else None
+    lp = _ptr_list(logits) if logits is not None else None
+    loss = None
+    partials = None
+    dlog = None
+    if tags is not None:
+        loss = hip.PairLoss()
+        partials = torch.empty((lib().peneo_pair_loss_partials_save(B, N), 32), dtype=torch.float32, device=ab.device)
+        if want_dlogits:
+            dlog = [torch.empty((B, P, c), dtype=torch.float32, device=ab.device) for c in classes]
+        for h in range(nh):
+            assert tags[h].dtype == torch.int64 and tags[h].shape == (B, P)
+            loss.tags[h] = ptr(_c(tags[h]))
+            loss.class_weight[h] = ptr(class_weights[h]) if class_weights is not None else None
+            if dlog is not None:
+                loss.dlogits[h] = ptr(dlog[h])
+        loss.partials = ptr(partials)
+    if save_buffers is not None:
+        act, x_rows = save_buffers
+        assert act.dtype == torch.uint8 and act.numel() >= lib().peneo_pair_save_bytes(B, N, nh, D) and act.is_contiguous()
+        assert x_rows.shape == (B * pair_bwd_rows(N), D) and x_rows.dtype == ab.dtype and x_rows.is_contiguous()
+    else:
+        act = torch.empty(lib().peneo_pair_save_bytes(B, N, nh, D), dtype=torch.uint8, device=ab.device)
+        x_rows = torch.empty((B * pair_bwd_rows(N), D), dtype=ab.dtype, device=ab.device)
+    with kernel_timer("pair_heads_fwd_mxfp8_save"):
+        check(lib().peneo_pair_heads_fwd_mxfp8_save(ptr(ab), B, N, C.byref(desc), lp, C.byref(loss) if loss is not None else None,
+                                                    ptr(act), ptr(x_rows), stream()), "peneo_pair_heads_fwd_mxfp8_save")
+    return logits, partials, dlog, (act, x_rows)
+
+
 def pair_x_fwd(ab_doc: torch.Tensor, i0: int, i1: int, out: torch.Tensor, pre: Optional[torch.Tensor] = None) -> torch.Tensor:
     """x = SiLU(a_i + b_j) for the pairs of rows i0..i1; `pre` (same shape) optionally receives a_i + b_j."""
     N, D2 = ab_doc.shape
