@@ -55,6 +55,11 @@ const char* peneo_last_error(void);
  *     wgrad    dW = dy^T x    -> (0, 0)
  * Epilogue order:  v = alpha*acc (+bias[n]) ; preact <- v ; v = act(v) ; v *= act'(grad_src[m,n]) ;
  *                  dropout ; v += residual[m,n] ; v += C[m,n] if accumulate ; C <- v
+ * Kernel choice for bf16 operands that meet the LDS-DMA conditions (16-byte aligned bases and rows): (1, *) the persistent launch or the
+ * 8-wave big tiles where their rules pick the problem, else 128 x 128 tiles; (0, 0) a wgrad whose C is fp32 and made of whole
+ * 384 x 192 tiles, with no epilogue option beyond accumulate, no a_colsum, K % 64 == 0 and K >= 65536 runs tiles x split_k
+ * one-per-CU workgroups on 384 x 192 tiles (the pair heads' dW1; peneo_gemm_set_nn384_mode below), every other one 128 x 128 tiles.
+ * A split reduction sums its slices in slice order on every path.
  * Replaces torch.nn.Linear / F.linear call sites: modeling_layoutlmv3.py:292-294,335-360,
  * RobertaSelfOutput/Intermediate/Output, peneo_decoder.py:126,213-222 and their autograd.
  * ------------------------------------------------------------------------------------------ */
@@ -766,6 +771,22 @@ int peneo_spots_compact_batch(const peneo_spots_batch_desc* desc, int B, int N, 
  * choice (default; also set by PENEO_GEMM_BIG), 256 / 384 / 128 = force one big-tile shape where its constraints hold.  A plain
  * global: set it while no peneo_gemm call is in flight on any thread.  Used by the kernel tests and tools/ only. */
 void peneo_gemm_set_big_mode(int mode);
+int peneo_gemm_big_mode(void);            /* the mode in force (tests restore what they found) */
+/* The same for weight gradients with A = [K, M] and B = [K, N] (gemm_big.hip, 384 x 192 tiles x split_k one-per-CU workgroups whose
+ * fp32 partials the split-k reduce sums in slice order).  The rule: bf16 operands, fp32 C, no epilogue option beyond accumulate,
+ * no a_colsum, M % 384 == 0, N % 192 == 0, K % 64 == 0, 16-byte aligned operands, and K >= 65536 (the pair heads' dW1; every
+ * other caller keeps the 128 x 128 kernel).  0 = off, 1 = that rule (default; also set by PENEO_GEMM_NN384), 2 = the rule without
+ * its bound on K (tests, tools).  PENEO_GEMM_BIG = 0 / peneo_gemm_set_big_mode(0) switches it off as well.
+ * Diagnostics like the setter above (process-wide plain globals, not thread-safe, for tests, tools and the decoder's split choice):
+ * peneo_gemm_nn384_mode: the mode in force (0 while big tiles are off).  peneo_gemm_nn384_launches: how many peneo_gemm calls of
+ * this process took the path (the 128 x 128 kernel sums the same k-steps in the same order, so a result cannot tell which ran).
+ * peneo_gemm_nn384_shape_ok: 1 if the SHAPE part of the rule holds for (M, N, K) under the mode in force - the library's one copy of
+ * 384 / 192 / 64 / 65536; a call with that shape still keeps the 128 x 128 kernel when its layouts, C type, epilogue or the
+ * alignment of an operand (16-byte bases, lda % 8, ldb % 8, ldc % 4, 64 rows of A or B below 2 GiB) are outside the rule. */
+void peneo_gemm_set_nn384_mode(int mode);
+int peneo_gemm_nn384_mode(void);
+uint64_t peneo_gemm_nn384_launches(void);
+int peneo_gemm_nn384_shape_ok(int M, int N, int K);
 /* The same for the persistent launch (gemm_sk.hip; first choice of peneo_gemm for large bf16 problems with k-major A and B):
  * 0 = off (the tiled kernels above), 1 = the measured rules (default; also set by PENEO_GEMM_SK), F * 1000 + BN = force ranges of
  * whole 32 F x BN tiles, + 100000 = force ranges that cut tiles (stream-k), wherever the kernel's constraints hold (B k-major among

@@ -1024,6 +1024,12 @@ extern "C" int peneo_gemm(int dtype, int a_kmajor, int b_kmajor, int M, int N, i
     if (big == 0) big = launch_gemm_big(p, b_kmajor != 0, st);
     if (big < 0) return big;
     launched = big == 1;
+  } else if (dtype == PENEO_BF16 && !a_kmajor && !b_kmajor && dma_ok(A, lda, false, M, K) && dma_ok(B, ldb, false, N, K)) {
+    // deep weight gradients whose output is whole 384 x 192 tiles (the pair heads' dW1): tiles x split_k one-per-CU workgroups
+    // (gemm_big.hip, launch_gemm_big_nn holds the rule); the partials are reduced below like the 128 x 128 kernel's
+    const int big = launch_gemm_big_nn(p, st);
+    if (big < 0) return big;
+    launched = big == 1;
   }
   if (launched) {
   } else if (dtype == PENEO_BF16 && dma_ok(A, lda, a_kmajor != 0, M, K) && dma_ok(B, ldb, b_kmajor != 0, N, K))

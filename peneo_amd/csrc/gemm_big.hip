@@ -8,6 +8,7 @@
 // N = 2304, 240 tiles of 384 x 192 for N = 3072, 138 tiles of 256 x 128 for N = 768).
 //
 // Layouts: A k-major [M][K]; B k-major [N][K] (forward, x W^T) or mn-major [K][N] (dgrad, dy W).  K % 64 == 0.
+// Both mn-major (A [K][M], B [K][N]: a weight gradient dy^T x) on the 384 x 192 tile, with split-k: launch_gemm_big_nn below.
 // LDS image of a k-major tile: rows of 128 B (64 k), 16-byte slot s of row r at slot s ^ ((r >> 1) & 7) (swizzle applied
 // to the SOURCE address of each LDS-DMA lane, destination lane-linear: 1 KiB piece = 8 rows); fragments by ds_read_b128.
 // mn-major tile: 1 KiB pieces of [8 k][64 columns], the two 64-byte halves of a line swapped when (k >> 1) & 1; fragments
@@ -25,9 +26,9 @@ namespace peneo {
 
 typedef short bg_s16x4 __attribute__((ext_vector_type(4)));
 
-template <bool BK_, int WGM_, int WGN_, int FM_, int FN_, int NSTAGE_>
+template <bool BK_, int WGM_, int WGN_, int FM_, int FN_, int NSTAGE_, bool AK_ = true>
 struct BigCfg {
-  static constexpr bool BK = BK_;
+  static constexpr bool AK = AK_, BK = BK_;
   static constexpr int WGM = WGM_, WGN = WGN_, FM = FM_, FN = FN_, NSTAGE = NSTAGE_;
   static constexpr int BM = WGM * FM * 32, BN = WGN * FN * 32;
   static constexpr int A_BYTES = BM * 128, B_BYTES = BN * 128, STAGE = A_BYTES + B_BYTES;
@@ -40,7 +41,10 @@ struct BigCfg {
   static_assert(LDS_BYTES <= 160 * 1024, "LDS");
 };
 
-template <typename C>
+// PART: the launch is tiles x split_k workgroups, workgroup (tile, z) multiplies k-tiles [z kt_per_split, (z + 1) kt_per_split) and
+// leaves its tile as plain fp32 in slice z of p.ws (peneo_gemm's split-k reduce runs the caller's epilogue).  Its own
+// instantiation: the fused epilogue is not part of its code.
+template <typename C, bool PART = false>
 __global__ __launch_bounds__(512) void gemm_big_kernel(GemmParams p, int tiles_n) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int FM = C::FM, FN = C::FN, NSTAGE = C::NSTAGE;
@@ -51,21 +55,37 @@ __global__ __launch_bounds__(512) void gemm_big_kernel(GemmParams p, int tiles_n
   // XCD-aware tile order: workgroup ids go round-robin to the 8 XCDs; every XCD gets a contiguous band of tiles, n fastest
   const int total = gridDim.x, lin = blockIdx.x;
   const int q8 = total >> 3, r8 = total & 7, xcd = lin & 7, slot = lin >> 3;
-  const int tile = xcd * q8 + min(xcd, r8) + slot;
+  int tile = xcd * q8 + min(xcd, r8) + slot;
+  // (PART: the order above runs over the whole launch, slice-major: the tiles of one k-range are neighbours on an XCD)
+  int zsplit = 0, kt0 = 0, ktiles = p.K / 64;
+  if constexpr (PART) {
+    const int tiles = total / p.split_k;
+    zsplit = tile / tiles;
+    tile -= zsplit * tiles;
+    kt0 = zsplit * p.kt_per_split;
+    ktiles = min(ktiles, kt0 + p.kt_per_split) - kt0;
+  }
   const int m0 = (tile / tiles_n) * C::BM, n0 = (tile % tiles_n) * C::BN;
 
   const bf16_t* A = reinterpret_cast<const bf16_t*>(p.A);
   const bf16_t* B = reinterpret_cast<const bf16_t*>(p.B);
-  const int ktiles = p.K / 64;
 
   // ---- LDS-DMA sources of this wave's pieces (piece g = wave + 8 u of the A tile / of the B tile): per-lane 32-bit byte
   //      offsets inside the tile (constant over k) + one uniform 64-bit base per operand that walks k with scalar adds ----
   uint32_t offA[C::APW], offB[C::BPW];
 #pragma unroll
   for (int u = 0; u < C::APW; ++u) {
-    const int row = (wave + 8 * u) * 8 + (lane >> 3);
-    const int sg = (lane & 7) ^ ((row >> 1) & 7);
-    offA[u] = (uint32_t)(((int64_t)(min(m0 + row, p.M - 1) - m0) * p.lda + sg * 8) * 2);
+    const int g = wave + 8 * u;
+    if constexpr (C::AK) {
+      const int row = g * 8 + (lane >> 3);
+      const int sg = (lane & 7) ^ ((row >> 1) & 7);
+      offA[u] = (uint32_t)(((int64_t)(min(m0 + row, p.M - 1) - m0) * p.lda + sg * 8) * 2);
+    } else {
+      constexpr int MQ = C::BM / 64;
+      const int kb = g / MQ, mq = g % MQ, kr = lane >> 3;
+      const int cg = (lane & 7) ^ (((kr >> 1) & 1) << 2);
+      offA[u] = (uint32_t)(((int64_t)(kb * 8 + kr) * p.lda + (min(m0 + mq * 64 + cg * 8, p.M - 8) - m0)) * 2);
+    }
   }
 #pragma unroll
   for (int u = 0; u < C::BPW; ++u) {
@@ -86,9 +106,10 @@ __global__ __launch_bounds__(512) void gemm_big_kernel(GemmParams p, int tiles_n
     const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
     return reinterpret_cast<const char*>(((uint64_t)hi << 32) | lo);
   };
-  const char* bA = uniform_ptr(A + (int64_t)m0 * p.lda);
-  const char* bB = uniform_ptr(C::BK ? B + (int64_t)n0 * p.ldb : B + n0);
+  const int64_t stepA = C::AK ? 128 : (int64_t)64 * p.lda * 2;
   const int64_t stepB = C::BK ? 128 : (int64_t)64 * p.ldb * 2;
+  const char* bA = uniform_ptr(reinterpret_cast<const char*>(C::AK ? A + (int64_t)m0 * p.lda : A + m0) + kt0 * stepA);
+  const char* bB = uniform_ptr(reinterpret_cast<const char*>(C::BK ? B + (int64_t)n0 * p.ldb : B + n0) + kt0 * stepB);
   const uint32_t lds0 = lds_addr(smem);
   // The pieces of a k-tile are issued in four groups, one between the MFMA clusters of each k-step: a wave that issues
   // all of its pieces back to back stalls on the memory pipeline (measured: fill and compute then run one after the other,
@@ -102,7 +123,7 @@ __global__ __launch_bounds__(512) void gemm_big_kernel(GemmParams p, int tiles_n
       if (u < C::APW) lds_dma_1k_s<0>(offA[u], bA, dbase + u * 8192);
       else lds_dma_1k_s<0>(offB[u - C::APW], bB, dbase + C::A_BYTES + (u - C::APW) * 8192);
     }
-    if constexpr (G == 3) { bA += 128; bB += stepB; }      // the k-tile is complete: the bases move on
+    if constexpr (G == 3) { bA += stepA; bB += stepB; }      // the k-tile is complete: the bases move on
   };
   auto issue = [&](int stage) {
     dbase = __builtin_amdgcn_readfirstlane(lds0 + stage * C::STAGE + wave * 1024);
@@ -111,11 +132,17 @@ __global__ __launch_bounds__(512) void gemm_big_kernel(GemmParams p, int tiles_n
   };
 
   // ---- fragment offsets inside a stage ----
-  int aoff[4], boff[C::BK ? 4 : FN];
-  {
+  int aoff[C::AK ? 4 : FM], boff[C::BK ? 4 : FN];
+  if constexpr (C::AK) {
     const int row = wm * FM * 32 + (lane & 31), swz = (row >> 1) & 7;
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) aoff[ks] = row * 128 + (((2 * ks + half) ^ swz) << 4);
+  } else {
+#pragma unroll
+    for (int i = 0; i < FM; ++i) {
+      const int m = wm * FM * 32 + i * 32 + 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
+      aoff[i] = (half * (C::BM / 64) + (m >> 6)) * 1024 + ((lane & 15) >> 2) * 128 + (((m & 63) * 2) ^ (((lane >> 3) & 1) << 6));
+    }
   }
   if constexpr (C::BK) {
     const int row = wn * FN * 32 + (lane & 31), swz = (row >> 1) & 7;
@@ -140,7 +167,18 @@ __global__ __launch_bounds__(512) void gemm_big_kernel(GemmParams p, int tiles_n
 
   auto load_a = [&](const char* st, int ks, uint4 (&fa)[FM]) {
 #pragma unroll
-    for (int i = 0; i < FM; ++i) fa[i] = *reinterpret_cast<const uint4*>(st + aoff[ks] + i * 4096);
+    for (int i = 0; i < FM; ++i) {
+      if constexpr (C::AK) {
+        fa[i] = *reinterpret_cast<const uint4*>(st + aoff[ks] + i * 4096);
+      } else {
+        typedef __attribute__((address_space(3))) bg_s16x4* lds_s4p;
+        const char* q = st + aoff[i] + ks * (2 * (C::BM / 64) * 1024);
+        const bg_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4p)(q));
+        const bg_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4p)(q + 512));
+        const uint2 l2 = __builtin_bit_cast(uint2, lo), h2 = __builtin_bit_cast(uint2, hi);
+        fa[i] = make_uint4(l2.x, l2.y, h2.x, h2.y);
+      }
+    }
   };
   auto load_b = [&](const char* st, int ks, uint4 (&fb)[FN]) {
 #pragma unroll
@@ -223,7 +261,12 @@ __global__ __launch_bounds__(512) void gemm_big_kernel(GemmParams p, int tiles_n
         const float4 x0 = *reinterpret_cast<const float4*>(patch + rl * C::EP_LD + cgi * 8);
         const float4 x1 = *reinterpret_cast<const float4*>(patch + rl * C::EP_LD + cgi * 8 + 4);
         v[0] = x0.x; v[1] = x0.y; v[2] = x0.z; v[3] = x0.w; v[4] = x1.x; v[5] = x1.y; v[6] = x1.z; v[7] = x1.w;
-        epilogue_store8(p, mb + rl, nb, v);
+        if constexpr (PART) {
+          float4* q = reinterpret_cast<float4*>(p.ws + ((int64_t)zsplit * p.M + (mb + rl)) * p.N + nb);
+          q[0] = x0; q[1] = x1;
+        } else {
+          epilogue_store8(p, mb + rl, nb, v);
+        }
       }
     }
     __builtin_amdgcn_wave_barrier();
@@ -235,15 +278,16 @@ __global__ __launch_bounds__(512) void gemm_big_kernel(GemmParams p, int tiles_n
   static_assert(FM <= 4, "row blocks");
 }
 
-template <typename C>
+template <typename C, bool PART = false>
 static int launch_big(const GemmParams& p, hipStream_t st) {
   const int tm = (p.M + C::BM - 1) / C::BM, tn = (p.N + C::BN - 1) / C::BN;
   static std::atomic<uint64_t> lds_devices{0};
-  if (!allow_dynamic_lds(reinterpret_cast<const void*>(gemm_big_kernel<C>), C::LDS_BYTES, lds_devices)) {
+  if (!allow_dynamic_lds(reinterpret_cast<const void*>(gemm_big_kernel<C, PART>), C::LDS_BYTES, lds_devices)) {
     set_error("peneo_gemm: cannot raise dynamic LDS to %d bytes", C::LDS_BYTES);
     return PENEO_ERR_LAUNCH;
   }
-  hipLaunchKernelGGL(gemm_big_kernel<C>, dim3((unsigned)(tm * tn)), dim3(512), C::LDS_BYTES, st, p, tn);
+  const int wgs = tm * tn * (PART ? p.split_k : 1);
+  hipLaunchKernelGGL((gemm_big_kernel<C, PART>), dim3((unsigned)wgs), dim3(512), C::LDS_BYTES, st, p, tn);
   const int rc = check_launch("peneo_gemm (big tiles)");
   return rc == PENEO_OK ? 1 : rc;
 }
@@ -279,6 +323,8 @@ int launch_gemm_big(const GemmParams& p, bool b_kmajor, hipStream_t st) {
   // mn-major B = the dgrad GEMMs of the backward: in the step they run beside the weight-gradient stream, and a workgroup that
   // needs a CU's whole LDS cannot share it (measured: d_zi on 384 x 192 tiles 50 us alone, 166 us in the step; the step is
   // 0.2 ms FASTER with the 128 x 128 kernel there).  A forced tile (tools) still runs them.
+  // (Those are SHORT launches that wait for empty CUs each time.  The one LONG launch of the step, the pair heads' dW1 on the side
+  // stream, does run on whole-LDS workgroups: launch_gemm_big_nn.)
   if (!b_kmajor && g_big_mode == 1) return 0;
   if (p.split_k > 1 || p.dz_on || p.K % 64 != 0 || p.K < 128 || p.N % 8 != 0) return 0;
   if ((reinterpret_cast<uintptr_t>(p.A) | reinterpret_cast<uintptr_t>(p.B)) & 15) return 0;
@@ -314,7 +360,64 @@ int launch_gemm_big(const GemmParams& p, bool b_kmajor, hipStream_t st) {
   return launch_big<Big256<false>>(p, st);
 }
 
+// ---- weight gradients with both operands mn-major: C[M][N] = A[K][M]^T B[K][N] on 384 x 192 tiles with split-k ----
+// The pair heads' dW1 = dz^T x (M = 5 x 384, N = 384, K = all pairs of the batch) is the deepest contraction of the step and
+// fill-bound on the 128 x 128 kernel (32 KiB staged per 2.1 MFLOP); 1920 x 384 is exactly 5 x 2 tiles of 384 x 192, which stage
+// 72 KiB per 9.4 MFLOP: half the bytes.  tiles x split_k one-per-CU workgroups; partials leave as plain fp32 (PART) and
+// peneo_gemm's split-k reduce applies `accumulate`.
+// Taken only when ALL hold (everything else stays on its kernel): fp32 C, no epilogue option beyond accumulate, no a_colsum,
+// M % 384 == 0, N % 192 == 0, K % 64 == 0, 16-byte aligned C / workspace rows, and K >= NN_MIN_K.
+//   NN_MIN_K = 65536: the other (mn, mn) callers contract over the tokens of a batch (encoder / patch-embedding / decoder-input
+//   weight gradients: K <= 8192 at every configuration), where the 128 x 128 kernel's M N / 16384 tiles x its own split fill the
+//   chip and a workgroup's range is a few k-tiles; dW1 contracts over pairs (K = 8256 per document of 128 lines, 1 081 344 at the
+//   benchmark shape), where a range is hundreds of k-tiles and the 144 KiB ring's prologue and the partial store are noise.
+using BigNN384 = BigCfg<false, 4, 2, 3, 3, 2, false>;
+constexpr int NN_MIN_K = 65536;
+
+static int g_nn_mode = -1;    // PENEO_GEMM_NN384: 0 = off, 1 = by the rule above (default), 2 = without the K bound (tests, tools)
+
+static std::atomic<uint64_t> g_nn_launches{0};   // calls that took the path (the tests' proof of routing: the 128 x 128 kernel sums
+                                                 // the same k-steps in the same order, so the results alone cannot tell)
+
+static int nn_mode() {
+  if (g_nn_mode < 0) { const char* e = getenv("PENEO_GEMM_NN384"); g_nn_mode = e ? atoi(e) : 1; }
+  if (g_big_mode < 0) { const char* e = getenv("PENEO_GEMM_BIG"); g_big_mode = e ? atoi(e) : 1; }
+  return g_big_mode == 0 ? 0 : g_nn_mode;      // PENEO_GEMM_BIG=0 switches every big-tile path off
+}
+
+// the shape part of the rule under the mode in force: the one copy, also what a caller sizes its split-k by (peneo_gemm_nn384_shape_ok)
+static bool nn_shape_ok(int M, int N, int K) {
+  const int mode = nn_mode();
+  if (mode == 0 || M <= 0 || N <= 0 || K <= 0) return false;
+  if (M % BigNN384::BM != 0 || N % BigNN384::BN != 0 || K % 64 != 0) return false;
+  return mode != 1 || K >= NN_MIN_K;
+}
+
+int launch_gemm_big_nn(const GemmParams& p, hipStream_t st) {
+  if (!nn_shape_ok(p.M, p.N, p.K)) return 0;
+  const peneo_gemm_epilogue& e = p.ep;
+  if (p.c_dtype != PENEO_F32 || p.dz_on || e.bias || e.preact || e.grad_src || e.residual || e.a_colsum || e.act != PENEO_ACT_NONE ||
+      e.drop_p != 0.f || e.alpha != 1.f)
+    return 0;
+  if ((reinterpret_cast<uintptr_t>(p.A) | reinterpret_cast<uintptr_t>(p.B) | reinterpret_cast<uintptr_t>(p.C)) & 15) return 0;
+  if (p.lda % 8 != 0 || p.ldb % 8 != 0 || p.ldc % 4 != 0) return 0;
+  // per-lane source offsets are 32-bit: 64 rows of the operand
+  if ((int64_t)64 * p.lda * 2 >= ((int64_t)1 << 31) || (int64_t)64 * p.ldb * 2 >= ((int64_t)1 << 31)) return 0;
+  if (p.split_k > 1 && (p.ws == nullptr || (reinterpret_cast<uintptr_t>(p.ws) & 15))) return 0;
+  g_nn_launches.fetch_add(1, std::memory_order_relaxed);
+  return p.split_k > 1 ? launch_big<BigNN384, true>(p, st) : launch_big<BigNN384, false>(p, st);
+}
+
 }  // namespace peneo
 
 /* tools/ only (not in the header): 0 = off, 1 = choose by the cost model, 256 / 384 / 128 = force that tile shape */
 extern "C" void peneo_gemm_set_big_mode(int mode) { peneo::g_big_mode = mode; }
+extern "C" int peneo_gemm_big_mode(void) {
+  if (peneo::g_big_mode < 0) { const char* e = getenv("PENEO_GEMM_BIG"); peneo::g_big_mode = e ? atoi(e) : 1; }
+  return peneo::g_big_mode;
+}
+/* 0 = off, 1 = the rule of launch_gemm_big_nn, 2 = that rule without its bound on K */
+extern "C" void peneo_gemm_set_nn384_mode(int mode) { peneo::g_nn_mode = mode; }
+extern "C" int peneo_gemm_nn384_mode(void) { return peneo::nn_mode(); }
+extern "C" int peneo_gemm_nn384_shape_ok(int M, int N, int K) { return peneo::nn_shape_ok(M, N, K) ? 1 : 0; }
+extern "C" uint64_t peneo_gemm_nn384_launches(void) { return peneo::g_nn_launches.load(std::memory_order_relaxed); }

@@ -251,6 +251,9 @@ inline bool allow_dynamic_lds(const void* kernel, int bytes, std::atomic<uint64_
 
 // gemm_big.hip: 0 = the shape / options are not covered (the caller runs the 128 x 128 kernel), 1 = launched
 int launch_gemm_big(const GemmParams& p, bool b_kmajor, hipStream_t st);
+// gemm_big.hip, A = [K, M] and B = [K, N]: 384 x 192 tiles x p.split_k k-ranges (partials in p.ws when p.split_k > 1; the caller
+// reduces them).  Same return convention.
+int launch_gemm_big_nn(const GemmParams& p, hipStream_t st);
 // gemm_sk.hip (persistent stream-k launch): same return convention.  A launch whose ranges cut tiles keeps its flags and slabs in
 // the caller's workspace (ws, ws_bytes): at least gemm_sk_workspace_bytes(M, N, K) bytes, 16-byte aligned.
 int launch_gemm_sk(const GemmParams& p, bool b_kmajor, void* ws, size_t ws_bytes, hipStream_t st);

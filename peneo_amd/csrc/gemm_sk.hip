@@ -437,6 +437,11 @@ static int sk_groups() {
 static size_t sk_flag_bytes(int G) { return ((size_t)G * sizeof(uint32_t) + 255) & ~(size_t)255; }
 static size_t sk_scratch_bytes(int G, int F, int BN) { return sk_flag_bytes(G) + (size_t)G * (32 * F) * BN * sizeof(float); }
 
+__global__ void sk_zero_flags_kernel(uint32_t* flags, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) flags[i] = 0u;
+}
+
 // ws: null = ranges of whole tiles; else ranges of units that cut tiles (stream-k), flags and slabs in `ws`
 template <typename C, int EP>
 static int launch_sk_ep(const GemmParams& p, void* ws, hipStream_t st) {
@@ -466,11 +471,12 @@ static int launch_sk_ep(const GemmParams& p, void* ws, hipStream_t st) {
     set_error("peneo_gemm: cannot raise dynamic LDS to %d bytes", C::LDS_BYTES);
     return PENEO_ERR_LAUNCH;
   }
-  // every flag the launch polls starts at 0 (under a stream capture: a memset node ahead of the kernel)
-  if (pl.flags && hipMemsetAsync(pl.flags, 0, (size_t)G * sizeof(uint32_t), st) != hipSuccess) {
-    (void)hipGetLastError();
-    set_error("peneo_gemm: cannot clear the stream-k flags");
-    return PENEO_ERR_LAUNCH;
+  // every flag the launch polls starts at 0.  A kernel, not hipMemsetAsync: as a memset node of a captured graph it was replayed
+  // out of order with the stream's other work when another queue was busy (the replay's result stale or half written: DESIGN 16)
+  if (pl.flags) {
+    hipLaunchKernelGGL(sk_zero_flags_kernel, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, st, pl.flags, G);
+    const int zrc = check_launch("peneo_gemm (stream-k flags)");
+    if (zrc != PENEO_OK) return zrc;
   }
   hipLaunchKernelGGL((gemm_sk_kernel<C, EP>), dim3((unsigned)G), dim3(512), C::LDS_BYTES, st, p, pl);
   const int rc = check_launch("peneo_gemm (persistent)");

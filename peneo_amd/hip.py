@@ -202,6 +202,11 @@ SIGNATURES = {
     "peneo_spots_compact_batch_workspace_bytes": (_sz, [_i, _i, _i]),
     "peneo_spots_compact_batch": (_i, [C.POINTER(SpotsBatchDesc), _i, _i, _vp, _vp, _i, _vp, _sz, _vp]),
     "peneo_gemm_set_big_mode": (None, [_i]),    # diagnostics block of the header: process-wide, not thread-safe
+    "peneo_gemm_set_nn384_mode": (None, [_i]),
+    "peneo_gemm_nn384_mode": (_i, []),
+    "peneo_gemm_nn384_shape_ok": (_i, [_i, _i, _i]),
+    "peneo_gemm_big_mode": (_i, []),
+    "peneo_gemm_nn384_launches": (C.c_uint64, []),
     "peneo_gemm_set_sk_mode": (None, [_i]),
     "peneo_gemm_sk_set_prof": (None, [_vp]),
     "peneo_gemm_sk_set_max_groups": (None, [_i]),

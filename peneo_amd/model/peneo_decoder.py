@@ -412,9 +412,16 @@ class _DecoderStage(torch.autograd.Function):
                     # (D = 512: 80 tiles, i.e. ONE workgroup per tile from that target, would run 23 ms - longer than the 24-layer
                     # encoder backward it hides behind; no workgroup gets more than dw1_side_rows rows of K: split 2 / 3 / 4 / 6 at
                     # config 4: 30.5 / 31.1 / 32.8 / 32.7 ms per step)
+                    # (where peneo_gemm runs this product on 384 x 192 one-per-CU tiles -- nh D = 1920 x D = 384: 10 tiles --
+                    # the count is 10 x split workgroups, dw1_side_big_wgs of them: DESIGN 23 has the sweep)
+                    if ops.gemm_nn384_takes(nh * D, D, B * rows, dt):
+                        tiles, wgs = (nh * D // 384) * (D // 192), dec.dw1_side_big_wgs
+                    else:
+                        tiles, wgs = -(-nh * D // 128) * -(-D // 128), dec.dw1_side_wgs
+                    # (not held, or on the main stream below: the step pays the launch's alone-time, and ops.gemm picks the split of
+                    # a launch that has the chip to itself - one round of CUs on the 384 x 192 tiles, choose_split_k_nn384)
                     split = None if not can_hold else \
-                        dec.dw1_side_split or max(1, dec.dw1_side_wgs // (-(-nh * D // 128) * -(-D // 128)),
-                                                  -(-B * rows // dec.dw1_side_rows))
+                        dec.dw1_side_split or max(1, wgs // tiles, -(-B * rows // dec.dw1_side_rows))
                     with ops.kernel_timer("dw1_gemm"):
                         ops.gemm(dzbuf, xbuf1, a_kmajor=False, b_kmajor=False, out=dW1cat, split_k=split)
                 ctx.side_work = (side, (dzbuf, xbuf1, dW1cat, ab), can_hold)
@@ -722,6 +729,8 @@ class PEneoDecoder(nn.Module):
         self.dw1_side_split = int(os.environ.get("PENEO_DW1_SPLIT", "0"))   # fixed split-k of that GEMM; 0: from the targets below
         self.dw1_side_rows = 600_000     # ... none of them with more rows of K than this
         self.dw1_side_wgs = 144          # ... of about this many long workgroups (measured 18.10 ms per step against 18.56 at 495)
+        self.dw1_side_big_wgs = 60       # ... of this many 8-wave workgroups where the GEMM runs on 384 x 192 tiles (10 tiles x split 6:
+        #     15.19 ms per step against 15.67 / 15.51 / 15.46 at split 5 / 7 / 8 and 15.79 on the 128 x 128 kernel, profiles/r07_dw1_nn384.txt)
         self._ratio = {}
 
     def set_pair_heads_format(self, fmt: str) -> None:

@@ -124,6 +124,20 @@ def choose_split_k(M: int, N: int, K: int, dtype: torch.dtype) -> int:
     return max(1, min(kt // 4, 512 // tiles, 16))
 
 
+def gemm_nn384_takes(M: int, N: int, K: int, dtype: torch.dtype) -> bool:
+    """Whether peneo_gemm runs C[M, N] = A[K, M]^T B[K, N] (fp32 C, no epilogue option beyond accumulate, aligned operands) on
+    its 384 x 192 one-per-CU tiles (the rule of launch_gemm_big_nn, gemm_big.hip): a caller picks its split-k from that."""
+    return dtype == torch.bfloat16 and bool(lib().peneo_gemm_nn384_shape_ok(M, N, K))     # (the library holds the rule's numbers)
+
+
+def choose_split_k_nn384(M: int, N: int, K: int) -> int:
+    """Split-k of a launch on the 384 x 192 one-per-CU tiles that has the chip to itself: ONE round of the 256 CUs (10 tiles: split 25,
+    1.54 ms at the pair heads' dW1 against 2.50 / 1.94 at split 12 / 16 and 2.01 for the 128 x 128 kernel at ITS stand-alone split 11,
+    profiles/r07_dw1_nn384.txt), at least 8 k-tiles per workgroup."""
+    tiles = (M // 384) * (N // 192)
+    return max(1, min(K // 64 // 8, 256 // tiles))
+
+
 def gemm(a: torch.Tensor, b: torch.Tensor, *, a_kmajor: bool = True, b_kmajor: bool = True,
          bias: Optional[torch.Tensor] = None, act: int = ACT_NONE, residual: Optional[torch.Tensor] = None,
          preact: Optional[torch.Tensor] = None, grad_src: Optional[torch.Tensor] = None, grad_act: int = ACT_NONE,
@@ -169,7 +183,14 @@ def gemm(a: torch.Tensor, b: torch.Tensor, *, a_kmajor: bool = True, b_kmajor: b
         ep.pair_dz, ep.pair_dz_ws = C.cast(C.pointer(pair_dz), C.c_void_p), ptr(pair_dz_ws)
         split_k = 1
     if split_k is None:
-        split_k = choose_split_k(M, N, K, a.dtype)
+        # (the shape and option part of launch_gemm_big_nn's rule; a misaligned operand keeps the 128 x 128 kernel at a split that is
+        # merely not its best)
+        plain = (bias is None and act == ACT_NONE and residual is None and preact is None and grad_src is None and alpha == 1.0
+                 and drop_p == 0.0 and a_colsum is None and pair_dz is None)
+        if not a_kmajor and not b_kmajor and plain and out.dtype == torch.float32 and gemm_nn384_takes(M, N, K, a.dtype):
+            split_k = choose_split_k_nn384(M, N, K)
+        else:
+            split_k = choose_split_k(M, N, K, a.dtype)
     # split-k partials, or the flags and slabs of a stream-k launch (which may need them with split_k == 1)
     ws_bytes = lib().peneo_gemm_workspace_bytes(M, N, K, split_k)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=a.device) if ws_bytes else None
