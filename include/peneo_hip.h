@@ -663,6 +663,23 @@ int peneo_grad_sqnorm(const peneo_adamw_tensor* table_dev, const int32_t* chunk_
 int peneo_adamw_step_clip(const peneo_adamw_tensor* table_dev, const int32_t* chunk_tensor_dev, const int32_t* chunk_index_dev,
                           int n_chunks, float beta1, float beta2, float eps, int step, const double* sqnorm_dev,
                           float max_grad_norm, peneo_stream_t stream);
+/* The step that also writes the parameters' working copies: peneo_adamw_step_clip, and for every element the UPDATED
+ * parameter value additionally goes to dst[i] of each emission record of its tensor -- the bf16 (or fp32) copies that the
+ * forward would otherwise rebuild with peneo_cast / peneo_cast_multi in a second pass over the memory this kernel has just
+ * streamed.  A record names a tensor of the AdamW table, a destination and its dtype (PENEO_BF16 / PENEO_F32); bf16 is
+ * rounded exactly as peneo_cast rounds, so dst equals a cast of the stored parameter bit for bit.  dst is a contiguous run
+ * of the tensor's numel elements that may sit anywhere inside a larger buffer (a row block of a stacked [3H, H] QKV
+ * matrix, a slice of a concatenated bias vector): it only needs the alignment of its element type, the kernel picks vector
+ * or element stores per record.  Layout: `emits_dev` holds the records sorted by tensor, `emit_first_dev` has one entry per
+ * tensor of the table plus one: the records of tensor k are emits_dev[emit_first_dev[k] .. emit_first_dev[k + 1]) -- none,
+ * one or any number per tensor (`tensor` repeats k; it is what a builder sorts by).  Both arrays live in device memory.
+ * Parameters and moments come out bit-identical to peneo_adamw_step_clip.  emits_dev == emit_first_dev == NULL: no
+ * emission (== peneo_adamw_step_clip). */
+typedef struct peneo_adamw_emit { void* dst; int32_t tensor; int32_t dtype; } peneo_adamw_emit;
+int peneo_adamw_step_emit(const peneo_adamw_tensor* table_dev, const int32_t* chunk_tensor_dev, const int32_t* chunk_index_dev,
+                          int n_chunks, float beta1, float beta2, float eps, int step, const double* sqnorm_dev,
+                          float max_grad_norm, const peneo_adamw_emit* emits_dev, const int32_t* emit_first_dev,
+                          peneo_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Composite stages: ONE call enqueues every kernel of an encoder layer (bf16 path) -- the per-kernel entry points above
@@ -695,7 +712,7 @@ typedef struct peneo_encoder_layer_grads {
   float* dg2; float* db2;
 } peneo_encoder_layer_grads;
 /* sizeof of the structs shared with a binding: 0 peneo_gemm_epilogue, 1 peneo_encoder_layer, 2 peneo_encoder_layer_grads,
- * 3 peneo_encoder_layer_mxfp8 */
+ * 3 peneo_encoder_layer_mxfp8, 4 peneo_adamw_emit */
 size_t peneo_struct_bytes(int which);
 /* workspace of the layer's GEMMs (as peneo_gemm_workspace_bytes): which = 0 forward, 1 backward main stream (dgrads), 2 backward
  * side stream (wgrads) */

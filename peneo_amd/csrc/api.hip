@@ -26,5 +26,5 @@ int check_launch(const char* what) {
 
 }  // namespace peneo
 
-extern "C" int peneo_version(void) { return 105; }
+extern "C" int peneo_version(void) { return 106; }
 extern "C" const char* peneo_last_error(void) { return peneo::g_err; }

@@ -209,10 +209,16 @@ __global__ __launch_bounds__(256) void colsum_vec_kernel(const T* x, int64_t ldx
 // every group; block = one 4096-element chunk of one tensor, per-tensor lr / weight decay from the table
 constexpr int ADAMW_CHUNK = 4096;
 constexpr int GRAD_SQNORM_SLOTS = 64;     // partial sums of the gradient norm: 31 k blocks adding to ONE address took 0.39 ms (1.3 TB/s)
+// EMIT: the updated parameter also goes to the destinations of the tensor's emission records (peneo_adamw_step_emit: the
+// working-precision copies of the weights, written while the value is in a register); records of tensor k are
+// emits[emit_first[k] .. emit_first[k + 1])
+template <bool EMIT>
 __global__ __launch_bounds__(256) void adamw_kernel(const peneo_adamw_tensor* tab, const int32_t* chunk_tensor,
                                                     const int32_t* chunk_index, float beta1, float beta2, float eps,
-                                                    float bc1, float rsqrt_bc2, int step, const double* sqnorm, float max_norm) {
-  const peneo_adamw_tensor t = tab[chunk_tensor[blockIdx.x]];
+                                                    float bc1, float rsqrt_bc2, int step, const double* sqnorm, float max_norm,
+                                                    const peneo_adamw_emit* emits, const int32_t* emit_first) {
+  const int tensor = chunk_tensor[blockIdx.x];
+  const peneo_adamw_tensor t = tab[tensor];
   // global gradient-norm clipping (torch.nn.utils.clip_grad_norm_, what HF Trainer does at max_grad_norm = 1.0 every step):
   // the coefficient comes from the device-side sum of squares of peneo_grad_sqnorm; the gradients themselves stay untouched
   float clip = 1.0f;
@@ -257,6 +263,22 @@ __global__ __launch_bounds__(256) void adamw_kernel(const peneo_adamw_tensor* ta
       *reinterpret_cast<float4*>(t.exp_avg_sq + i) = *reinterpret_cast<const float4*>(v);
     } else {
       for (int e = 0; e < cnt; ++e) { t.param[i + e] = p[e]; t.exp_avg[i + e] = m[e]; t.exp_avg_sq[i + e] = v[e]; }
+    }
+    if constexpr (EMIT) {
+      // a destination is any contiguous run inside a larger buffer: aligned to its element size only, so each record decides
+      // between one vector store and element stores by its own address (i is a multiple of 4)
+      for (int r = emit_first[tensor]; r < emit_first[tensor + 1]; ++r) {
+        const peneo_adamw_emit em = emits[r];
+        if (em.dtype == PENEO_F32) {
+          float* d = reinterpret_cast<float*>(em.dst) + i;
+          if (cnt == 4 && (reinterpret_cast<uintptr_t>(d) & 15) == 0) *reinterpret_cast<float4*>(d) = *reinterpret_cast<const float4*>(p);
+          else for (int e = 0; e < cnt; ++e) d[e] = p[e];
+        } else {
+          bf16_t* d = reinterpret_cast<bf16_t*>(em.dst) + i;
+          if (cnt == 4 && (reinterpret_cast<uintptr_t>(d) & 7) == 0) *reinterpret_cast<uint2*>(d) = make_uint2(pack_bf16x2(p[0], p[1]), pack_bf16x2(p[2], p[3]));
+          else for (int e = 0; e < cnt; ++e) d[e] = f32_to_bf16(p[e]);
+        }
+      }
     }
   }
 }
@@ -335,9 +357,26 @@ extern "C" int peneo_adamw_step_clip(const peneo_adamw_tensor* table_dev, const 
   PENEO_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps >= 0.f, "peneo_adamw_step: bad hyper-parameters");
   PENEO_REQUIRE(!sqnorm_dev || max_grad_norm > 0.f, "peneo_adamw_step_clip: max_grad_norm must be positive");
   const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
-  hipLaunchKernelGGL(adamw_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, table_dev, chunk_tensor_dev, chunk_index_dev,
-                     beta1, beta2, eps, (float)bc1, (float)(1.0 / sqrt(bc2)), step, sqnorm_dev, max_grad_norm);
+  hipLaunchKernelGGL(adamw_kernel<false>, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, table_dev, chunk_tensor_dev, chunk_index_dev,
+                     beta1, beta2, eps, (float)bc1, (float)(1.0 / sqrt(bc2)), step, sqnorm_dev, max_grad_norm, nullptr, nullptr);
   return check_launch("peneo_adamw_step");
+}
+
+extern "C" int peneo_adamw_step_emit(const peneo_adamw_tensor* table_dev, const int32_t* chunk_tensor_dev, const int32_t* chunk_index_dev,
+                                     int n_chunks, float beta1, float beta2, float eps, int step, const double* sqnorm_dev,
+                                     float max_grad_norm, const peneo_adamw_emit* emits_dev, const int32_t* emit_first_dev,
+                                     peneo_stream_t stream) {
+  if (!emits_dev && !emit_first_dev)   // nothing to emit: the plain step
+    return peneo_adamw_step_clip(table_dev, chunk_tensor_dev, chunk_index_dev, n_chunks, beta1, beta2, eps, step, sqnorm_dev, max_grad_norm,
+                                 stream);
+  PENEO_REQUIRE(table_dev && chunk_tensor_dev && chunk_index_dev && n_chunks > 0 && step >= 1, "peneo_adamw_step_emit: bad arguments");
+  PENEO_REQUIRE(emits_dev && emit_first_dev, "peneo_adamw_step_emit: the emission table needs both of its arrays");
+  PENEO_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps >= 0.f, "peneo_adamw_step_emit: bad hyper-parameters");
+  PENEO_REQUIRE(!sqnorm_dev || max_grad_norm > 0.f, "peneo_adamw_step_emit: max_grad_norm must be positive");
+  const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
+  hipLaunchKernelGGL(adamw_kernel<true>, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, table_dev, chunk_tensor_dev, chunk_index_dev,
+                     beta1, beta2, eps, (float)bc1, (float)(1.0 / sqrt(bc2)), step, sqnorm_dev, max_grad_norm, emits_dev, emit_first_dev);
+  return check_launch("peneo_adamw_step_emit");
 }
 
 extern "C" int peneo_adamw_step(const peneo_adamw_tensor* table_dev, const int32_t* chunk_tensor_dev, const int32_t* chunk_index_dev,

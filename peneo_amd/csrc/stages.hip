@@ -75,7 +75,7 @@ bool layer_ok(const peneo_encoder_layer* L) {
 
 extern "C" size_t peneo_struct_bytes(int which) {
   return which == 0 ? sizeof(peneo_gemm_epilogue) : which == 1 ? sizeof(peneo_encoder_layer) : which == 2 ? sizeof(peneo_encoder_layer_grads) :
-         which == 3 ? sizeof(peneo_encoder_layer_mxfp8) : 0;
+         which == 3 ? sizeof(peneo_encoder_layer_mxfp8) : which == 4 ? sizeof(peneo_adamw_emit) : 0;
 }
 
 extern "C" size_t peneo_encoder_layer_workspace_bytes(int rows, int H, int I, int which) {

@@ -69,6 +69,10 @@ class AdamwTensor(C.Structure):
                 ("weight_decay", _f), ("step_offset", _i), ("reserved", _i)]
 
 
+class AdamwEmit(C.Structure):
+    _fields_ = [("dst", _vp), ("tensor", _i), ("dtype", _i)]
+
+
 class EmbedTables(C.Structure):
     _fields_ = [("word", _vp), ("type0", _vp), ("pos", _vp), ("x", _vp), ("y", _vp), ("h", _vp), ("w", _vp),
                 ("coord_size", _i), ("shape_size", _i), ("max_2d", _i), ("vocab", _i), ("max_pos", _i)]
@@ -191,6 +195,7 @@ SIGNATURES = {
     "peneo_grad_sqnorm": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
     "peneo_grad_sqnorm_slots": (_i, []),
     "peneo_adamw_step_clip": (_i, [_vp, _vp, _vp, _i, _f, _f, _f, _i, _vp, _f, _vp]),
+    "peneo_adamw_step_emit": (_i, [_vp, _vp, _vp, _i, _f, _f, _f, _i, _vp, _f, _vp, _vp, _vp]),
     "peneo_struct_bytes": (C.c_size_t, [_i]),
     "peneo_encoder_layer_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i]),
     "peneo_encoder_layer_fwd": (_i, [_vp, _vp, _vp, C.c_size_t, _vp]),

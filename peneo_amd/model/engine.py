@@ -22,10 +22,21 @@ def bump_param_epoch() -> None:
 class WeightCache:
     """fp32 master parameters -> working-precision copies (cast / concatenated / re-packed on the
     device by libpeneo_hip kernels), refreshed whenever a parameter's ``_version`` changes, i.e.
-    after every optimizer step, and reused as-is during evaluation."""
+    after every optimizer step, and reused as-is during evaluation.
+
+    Entries made by ``cast`` / ``cat_rows`` / ``cat_vec`` are *declarative*: their content is a pure function of their source
+    parameters (a cast, a row stack of casts, a concatenation of fp32 vectors), every source owning one contiguous run of the
+    entry's buffer.  An optimizer that has the updated value in a register can write those runs itself
+    (``FusedAdamW(emit_into=model)``): ``declarative()`` hands out sources and destination views, ``mark_current()`` stamps
+    an entry it has rewritten.  Entries made through ``get`` directly (packing kernels, quantisers, the column split of
+    ``dec.ab``) are opaque and stay lazy.  ``builds[key]`` counts how often an entry was built by this cache."""
 
     def __init__(self) -> None:
         self._store: Dict[Tuple, Tuple[Tuple, object]] = {}
+        self._decl: Dict[Tuple, Tuple[str, tuple, list, list]] = {}   # key -> (builder, its arguments, sources, their views)
+        self._touched: set = set()           # declarative keys looked up since an optimizer last wrote them
+        self.gen = 0                         # bumped when a declarative entry appears or its buffer moves (an emission plan is stale)
+        self.builds: Dict[Tuple, int] = {}
 
     @staticmethod
     def _stamp(params: Sequence[torch.Tensor]) -> Tuple:
@@ -38,43 +49,97 @@ class WeightCache:
             return hit[1]
         val = build()
         self._store[key] = (stamp, val)
+        self.builds[key] = self.builds.get(key, 0) + 1
         return val
 
     def clear(self) -> None:
         self._store.clear()
+        self._decl.clear()
+        self._touched.clear()
+        self.gen += 1
+
+    # ---- declarative entries -----------------------------------------------------------------
+    def _declared(self, key: Tuple, builder: str, args: tuple, params: Sequence[torch.Tensor], alloc, views_of):
+        """Entry `key` = `alloc()` with every source cast into its view (`views_of(buffer)`, one per source)."""
+        self._touched.add(key)
+        stamp = self._stamp(params)
+        hit = self._store.get(key)
+        if hit is not None and hit[0] == stamp:
+            return hit[1]
+        buf = alloc()
+        views = views_of(buf)
+        for p, v in zip(params, views):
+            src = p.detach().contiguous()
+            if v.dtype == src.dtype and (v.data_ptr() | src.data_ptr()) % 16:
+                # a run inside a concatenation that starts off a 16-byte boundary (the 2- and 3-class biases of dec.b2):
+                # peneo_cast wants aligned vectors, the element-wise copy kernel takes any address
+                ops.copy2d(src.view(1, -1), out=v.view(1, -1))
+            else:
+                ops.cast(src, v.dtype, out=v)
+        self.put_declared(key, builder, args, params, buf, views)
+        return buf
+
+    def put_declared(self, key: Tuple, builder: str, args: tuple, params: Sequence[torch.Tensor], buf: torch.Tensor, views) -> None:
+        """Register a declarative entry somebody else has just filled (the model-wide multi-tensor cast)."""
+        old = self._decl.get(key)
+        if old is None or [v.data_ptr() for v in old[3]] != [v.data_ptr() for v in views]:
+            self.gen += 1
+        self._store[key] = (self._stamp(params), buf)
+        self._decl[key] = (builder, args, list(params), list(views))
+        self._touched.add(key)
+        self.builds[key] = self.builds.get(key, 0) + 1
+
+    def is_current(self, key: Tuple, params: Sequence[torch.Tensor]) -> bool:
+        hit = self._store.get(key)
+        return hit is not None and hit[0] == self._stamp(params)
+
+    def declarative(self):
+        """(key, source parameters, destination views) of every declarative entry in use: looked up since an optimizer
+        last wrote it, so the copies of a compute dtype that was switched away from drop out by themselves."""
+        return [(key, d[2], d[3]) for key, d in self._decl.items() if key in self._touched and key in self._store]
+
+    def builder_of(self, key: Tuple):
+        """(builder name, arguments): `getattr(cache, name)(*arguments)` builds the entry, in any cache."""
+        return self._decl[key][:2]
+
+    def mark_current(self, key: Tuple) -> None:
+        """The entry's buffer has just been rewritten from the current values of ALL its sources."""
+        self._store[key] = (self._stamp(self._decl[key][2]), self._store[key][1])
+        self._touched.discard(key)
 
     # ---- common builders -------------------------------------------------------------------
     def cast(self, name: str, p: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
         """Row-major working copy of one matrix (fp32 mode returns the parameter itself)."""
         if dtype == torch.float32:
             return p.detach()
-        return self.get((name, dtype), [p], lambda: ops.cast(p.detach().contiguous(), dtype))
+        return self._declared((name, dtype), "cast", (name, p, dtype), [p],
+                              lambda: torch.empty(p.shape, dtype=dtype, device=p.device), lambda buf: [buf])
 
     def cat_rows(self, name: str, ps: Sequence[torch.Tensor], dtype: torch.dtype) -> torch.Tensor:
         """[sum rows, K] working copy of several [rows_i, K] matrices stacked along dim 0."""
-        def build():
-            rows = sum(p.shape[0] for p in ps)
-            out = torch.empty((rows, ps[0].shape[1]), dtype=dtype, device=ps[0].device)
-            r = 0
+        def views_of(out):
+            views, r = [], 0
             for p in ps:
-                ops.cast(p.detach().contiguous(), dtype, out=out[r:r + p.shape[0]])
+                views.append(out[r:r + p.shape[0]])
                 r += p.shape[0]
-            return out
-        return self.get((name, dtype), list(ps), build)
+            return views
+        return self._declared((name, dtype), "cat_rows", (name, list(ps), dtype), list(ps),
+                              lambda: torch.empty((sum(p.shape[0] for p in ps), ps[0].shape[1]), dtype=dtype, device=ps[0].device),
+                              views_of)
 
     def cat_vec(self, name: str, ps: Sequence[Optional[torch.Tensor]], sizes: Sequence[int]) -> torch.Tensor:
-        """fp32 concatenation of bias vectors (None -> zeros)."""
+        """fp32 concatenation of bias vectors (None -> zeros, which no source ever overwrites)."""
         real = [p for p in ps if p is not None]
 
-        def build():
-            out = torch.zeros(sum(sizes), dtype=torch.float32, device=real[0].device)
-            r = 0
+        def views_of(out):
+            views, r = [], 0
             for p, n in zip(ps, sizes):
                 if p is not None:
-                    ops.cast(p.detach().contiguous(), torch.float32, out=out[r:r + n])
+                    views.append(out[r:r + n])
                 r += n
-            return out
-        return self.get((name, "vec"), real, build)
+            return views
+        return self._declared((name, "vec"), "cat_vec", (name, list(ps), list(sizes)), real,
+                              lambda: torch.zeros(sum(sizes), dtype=torch.float32, device=real[0].device), views_of)
 
 
 class DropoutSeeds:

@@ -336,7 +336,7 @@ def _describe_layer(model, st, idx, params, x, bufs):
     seeds = st.seeds
     site = 16 * (idx + 1)
     Wqkv = wc.cat_rows(f"L{idx}.qkv", [wq, wk, wv], dt)
-    bqkv = wc.get((f"L{idx}.bqkv",), [bq, bk, bv], lambda: torch.cat([bq.detach(), bk.detach(), bv.detach()]))
+    bqkv = wc.cat_vec(f"L{idx}.bqkv", [bq, bk, bv], [bq.numel(), bk.numel(), bv.numel()])
     Wo, Wi, Wo2 = wc.cast(f"L{idx}.o", wo, dt), wc.cast(f"L{idx}.i", wi, dt), wc.cast(f"L{idx}.o2", wo2, dt)
     L = EncoderLayer()
     L.Wqkv, L.bqkv, L.Wo, L.bo, L.g1, L.b1 = Wqkv.data_ptr(), bqkv.data_ptr(), Wo.data_ptr(), bo.data_ptr(), g1.data_ptr(), b1.data_ptr()
@@ -527,7 +527,7 @@ def _mx_layer_forward(model, st, idx, x, params):
             raise ValueError(f"mxfp8 encoder: rows = {R}, H = {H}, I = {I} is not supported by peneo_gemm_mxfp8")
         st.mx_scratch = _MxScratch(R, H, I, B * nh * T, dev)
     (Wqkv, Sqkv), (Wo, So), (Wi, Si), (Wo2, So2) = weights = _mx_weights(model, idx, params)
-    bqkv = wc.get((f"L{idx}.bqkv",), [bq, bk, bv], lambda: torch.cat([bq.detach(), bk.detach(), bv.detach()]))
+    bqkv = wc.cat_vec(f"L{idx}.bqkv", [bq, bk, bv], [bq.numel(), bk.numel(), bv.numel()])
     L, X = EncoderLayer(), EncoderLayerMxfp8()
     X.Wqkv_q, X.Wqkv_s, X.Wo_q, X.Wo_s = Wqkv.data_ptr(), Sqkv.data_ptr(), Wo.data_ptr(), So.data_ptr()
     X.Wi_q, X.Wi_s, X.Wo2_q, X.Wo2_s = Wi.data_ptr(), Si.data_ptr(), Wo2.data_ptr(), So2.data_ptr()
@@ -564,7 +564,7 @@ class _LayerStage(torch.autograd.Function):
         seeds = st.seeds
         site = 16 * (idx + 1)
         Wqkv = wc.cat_rows(f"L{idx}.qkv", [wq, wk, wv], dt)
-        bqkv = wc.get((f"L{idx}.bqkv",), [bq, bk, bv], lambda: torch.cat([bq.detach(), bk.detach(), bv.detach()]))
+        bqkv = wc.cat_vec(f"L{idx}.bqkv", [bq, bk, bv], [bq.numel(), bk.numel(), bv.numel()])
         Wo, Wi, Wo2 = wc.cast(f"L{idx}.o", wo, dt), wc.cast(f"L{idx}.i", wi, dt), wc.cast(f"L{idx}.o2", wo2, dt)
 
         qkv = ops.gemm(x, Wqkv, bias=bqkv)
@@ -865,12 +865,15 @@ class LayoutLMv3Model(nn.Module):
             groups.append(((f"L{i}.o", dt), [o_.dense.weight]))
             groups.append(((f"L{i}.i", dt), [layer.intermediate.dense.weight]))
             groups.append(((f"L{i}.o2", dt), [layer.output.dense.weight]))
-        params = [p for _, ps in groups for p in ps]
-        stamp = WeightCache._stamp(params)
-        if getattr(self, "_wstamp", None) == stamp:
+        # every entry current: nothing changed since the last forward, or an emitting optimizer step (FusedAdamW(emit_into=...))
+        # has written the copies itself and stamped them
+        stale = [k for k, (key, ps) in enumerate(groups) if not wc.is_current(key, ps)]
+        if not stale:
             return
+        params = [p for _, ps in groups for p in ps]
         plan = getattr(self, "_wplan", None)
         ptrs = tuple(p.data_ptr() for p in params)
+        whole = plan is None or plan[0] != ptrs or len(stale) == len(groups)
         if plan is None or plan[0] != ptrs:
             bufs, pairs = [], []
             for _, ps in groups:
@@ -882,10 +885,23 @@ class LayoutLMv3Model(nn.Module):
                 bufs.append(buf)
             plan = (ptrs, ops.CastPlan(pairs), bufs)
             self._wplan = plan
-        plan[1].run()
-        for (key, ps), buf in zip(groups, plan[2]):
-            wc._store[key] = (WeightCache._stamp(ps), buf)
-        self._wstamp = stamp
+        if whole:
+            plan[1].run()
+        for k in (range(len(groups)) if whole else stale):
+            (key, ps), buf = groups[k], plan[2][k]
+            views, r = [], 0
+            for p in ps:
+                views.append(buf[r:r + p.shape[0]])
+                r += p.shape[0]
+            if not whole:
+                # a few entries only (one parameter written from outside, an entry with a frozen source next to an emitting
+                # optimizer): their own casts, the current entries stay as they are
+                for p, v in zip(ps, views):
+                    ops.cast(p.detach().contiguous(), dt, out=v)
+            if len(ps) == 1:
+                wc.put_declared(key, "cast", (key[0], ps[0], dt), ps, buf, views)
+            else:
+                wc.put_declared(key, "cat_rows", (key[0], ps, dt), ps, buf, views)
 
     def forward(self, input_ids=None, bbox=None, attention_mask=None, image=None, **unused):
         if input_ids is None:

@@ -350,9 +350,9 @@ class _LiltLayerStage(torch.autograd.Function):
         site = 32 * (idx + 1)
         dev = x.device
         Wqkv = wc.cat_rows(f"L{idx}.qkv", [wq, wk, wv], dt)
-        bqkv = wc.get((f"L{idx}.bqkv",), [bq, bk, bv], lambda: torch.cat([bq.detach(), bk.detach(), bv.detach()]))
+        bqkv = wc.cat_vec(f"L{idx}.bqkv", [bq, bk, bv], [bq.numel(), bk.numel(), bv.numel()])
         Wlqkv = wc.cat_rows(f"L{idx}.lqkv", [lwq, lwk, lwv], dt)
-        blqkv = wc.get((f"L{idx}.blqkv",), [lbq, lbk, lbv], lambda: torch.cat([lbq.detach(), lbk.detach(), lbv.detach()]))
+        blqkv = wc.cat_vec(f"L{idx}.blqkv", [lbq, lbk, lbv], [lbq.numel(), lbk.numel(), lbv.numel()])
         grouped = _use_groups(dt, H, Hl, tp[4].shape[0], lp[4].shape[0])
         if grouped:
             qkv, lqkv = ops.gemm_group([(x, Wqkv, None, dict(bias=bqkv)), (l, Wlqkv, None, dict(bias=blqkv))])

@@ -225,7 +225,7 @@ class _DecoderStage(torch.autograd.Function):
         saved["s2"] = h
         # [a | b] = h [Wc[:, :D]; Wc[:, D:]]^T + [0 | bc]
         Wab = dec.stacked_combine_weight(wc_w, dt)
-        bab = wc.get(("dec.bab",), [wc_b], lambda: torch.cat([torch.zeros_like(wc_b.detach()), wc_b.detach()]))
+        bab = wc.cat_vec("dec.bab", [None, wc_b], [wc_b.numel(), wc_b.numel()])      # (zeros | bias)
         ab = ops.gemm(h, Wab, bias=bab).view(B, N, 2 * D)
         cws = [dec.le_loss.weight] + [dec.link_loss.weight] * 4 if tags is not None else None
         if kcls != 2:
@@ -240,8 +240,8 @@ class _DecoderStage(torch.autograd.Function):
             return tuple(outs) + tuple(logits)
         w1s, b1s = [hd[0] for hd in heads], [hd[1] for hd in heads]
         w2s, b2s = [hd[2] for hd in heads], [hd[3] for hd in heads]
-        b1cat = wc.get(("dec.b1",), b1s, lambda: torch.cat([b.detach() for b in b1s]))
-        b2cat = wc.get(("dec.b2",), b2s, lambda: torch.cat([b.detach() for b in b2s]))
+        b1cat = wc.cat_vec("dec.b1", b1s, [b.numel() for b in b1s])
+        b2cat = wc.cat_vec("dec.b2", b2s, [b.numel() for b in b2s])
         if dec.pair_heads_format == "mxfp8":
             # eval-only MXFP8 first layer (PEneoDecoder.forward has refused a forward with gradients); its own pack and cache key
             assert not need_grad
@@ -360,7 +360,7 @@ class _DecoderStage(torch.autograd.Function):
         w1s, b1s = [hd[0] for hd in heads], [hd[1] for hd in heads]
         w2s, b2s = [hd[2] for hd in heads], [hd[3] for hd in heads]
         W1cat = wc.cat_rows("dec.w1cat", w1s, dt)                      # [nh*D, D]
-        b1cat = wc.get(("dec.b1",), b1s, lambda: torch.cat([b.detach() for b in b1s]))
+        b1cat = wc.cat_vec("dec.b1", b1s, [b.numel() for b in b1s])
         dW1cat = torch.zeros((nh * D, D), dtype=torch.float32, device=dev)
         P = N * (N + 1) // 2
         w2d = [w.detach().contiguous() for w in w2s]

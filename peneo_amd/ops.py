@@ -241,6 +241,93 @@ class CastPlan:
               "peneo_cast_multi")
 
 
+class AdamwEmitTable:
+    """Emission table of ``peneo_adamw_step_emit`` for a fixed list of AdamW tensors (in the order of the ``peneo_adamw_tensor``
+    table): ``update(pairs)`` takes ``(parameter, destination view)`` pairs -- the step then also writes the updated parameter,
+    in the view's dtype, into the view -- and copies the table to the device only when the pairs differ from the last call's.
+    A pair's parameter is matched to the list by address and size, so a full view of a parameter counts as that parameter.
+    Any number of pairs may name one parameter.  ``ValueError``: a parameter that is not in the list, a destination that is
+    not contiguous, lives on another device, is neither bf16 nor fp32, or whose numel differs from the parameter's."""
+
+    def __init__(self, params: Sequence[torch.Tensor]):
+        self.params = list(params)
+        self.index = {(p.data_ptr(), p.numel()): k for k, p in enumerate(self.params)}
+        self.n_records = 0
+        self.keep: list = []                        # the destinations whose addresses the table holds
+        self._sig = None
+        self._dev = None
+
+    def reindex(self) -> bool:
+        """The parameters' storage may have moved (``p.data = ...``): match by their current addresses, rebuild on the next
+        update.  True when anything moved."""
+        index = {(p.data_ptr(), p.numel()): k for k, p in enumerate(self.params)}
+        if index == self.index:
+            return False
+        self.index, self._sig = index, None
+        return True
+
+    def records(self, pairs: Sequence[Tuple[torch.Tensor, torch.Tensor]]) -> List[Tuple[int, int, int]]:
+        """Validated (tensor, destination address, dtype code) records, sorted by tensor (host work only)."""
+        out = []
+        for p, dst in pairs:
+            k = self.index.get((p.data_ptr(), p.numel()))
+            if k is None:
+                raise ValueError("adamw emission: the parameter is not one of the step's tensors")
+            if dst.device != p.device:
+                raise ValueError(f"adamw emission: destination on {dst.device}, parameter on {p.device}")
+            if dst.dtype not in (torch.bfloat16, torch.float32):
+                raise ValueError(f"adamw emission: destination dtype {dst.dtype} is neither bf16 nor fp32")
+            if dst.numel() != p.numel():
+                raise ValueError(f"adamw emission: destination has {dst.numel()} elements, the parameter {p.numel()}")
+            if not dst.is_contiguous():
+                raise ValueError("adamw emission: the destination must be one contiguous run of elements")
+            out.append((k, dst.data_ptr(), dtype_code(dst.dtype)))
+        out.sort(key=lambda r: r[0])                # stable: a tensor's records keep the order of the pairs
+        return out
+
+    def update(self, pairs: Sequence[Tuple[torch.Tensor, torch.Tensor]]) -> None:
+        sig = tuple((p.data_ptr(), p.numel(), d.data_ptr(), d.dtype, d.numel()) for p, d in pairs)
+        if sig == self._sig:
+            return
+        recs = self.records(pairs)
+        n, nt = len(recs), len(self.params)
+        host = (hip.AdamwEmit * max(n, 1))()
+        first = (C.c_int32 * (nt + 1))()
+        for r, (k, addr, code) in enumerate(recs):
+            host[r].dst, host[r].tensor, host[r].dtype = addr, k, code
+            first[k + 1] += 1
+        for k in range(nt):
+            first[k + 1] += first[k]
+        raw = bytes(host) + bytes(first)            # one buffer, one H2D copy: [records | first]
+        if self._dev is None or self._dev.numel() != len(raw):
+            self._dev = torch.empty(len(raw), dtype=torch.uint8, device=self.params[0].device)
+        self._dev.copy_(torch.frombuffer(bytearray(raw), dtype=torch.uint8))
+        self._first_off = C.sizeof(host)
+        self.n_records, self.keep, self._sig = n, [d for _, d in pairs], sig
+
+    @property
+    def emits_ptr(self) -> int:
+        return self._dev.data_ptr()
+
+    @property
+    def first_ptr(self) -> int:
+        return self._dev.data_ptr() + self._first_off
+
+
+def adamw_step_emit(table: torch.Tensor, chunk_tensor: torch.Tensor, chunk_index: torch.Tensor, beta1: float, beta2: float,
+                    eps: float, step: int, emit: Optional[AdamwEmitTable], sqnorm: Optional[torch.Tensor] = None,
+                    max_grad_norm: float = 0.0) -> None:
+    """One fused AdamW step over the device table of ``hip.AdamwTensor`` (chunk maps as for ``peneo_adamw_step``) that also
+    writes the working copies named by ``emit``; ``emit`` None or empty: the plain step."""
+    if emit is not None and emit.n_records and emit._dev.device != table.device:
+        raise ValueError("adamw emission: the emission table lives on another device than the tensor table")
+    on = emit is not None and emit.n_records > 0
+    check(lib().peneo_adamw_step_emit(ptr(table), ptr(chunk_tensor), ptr(chunk_index), chunk_tensor.numel(), float(beta1),
+                                      float(beta2), float(eps), int(step), ptr(sqnorm), float(max_grad_norm),
+                                      emit.emits_ptr if on else None, emit.first_ptr if on else None, stream()),
+          "peneo_adamw_step_emit")
+
+
 def copy2d(src: torch.Tensor, out: Optional[torch.Tensor] = None, drop_p: float = 0.0, drop_seed: int = 0) -> torch.Tensor:
     assert src.dim() == 2 and src.stride(1) == 1
     if out is None:

@@ -1,5 +1,6 @@
 """Optimizer step of the training loop: fused multi-tensor AdamW on the C ABI
-(``peneo_adamw_step``) and the reference's four parameter groups.
+(``peneo_adamw_step``; ``peneo_adamw_step_emit`` when the step also writes the weights' working copies) and the reference's
+four parameter groups.
 
 Reference: ``PEneoTrainer.create_optimizer`` (pipeline/trainer.py:275-330) — parameters whose name contains
 ``"peneo_decoder"`` train at ``lr * peneo_downstream_speedup_ratio``; biases and LayerNorm weights get no weight
@@ -13,9 +14,9 @@ from typing import Dict, Iterable, List
 import torch
 import torch.nn as nn
 
-from . import hip
+from . import hip, ops
 from .hip import check, lib, ptr, stream
-from .model.engine import bump_param_epoch
+from .model.engine import WeightCache, bump_param_epoch
 
 
 def decay_parameter_names(model: nn.Module) -> List[str]:
@@ -57,14 +58,29 @@ class FusedAdamW(torch.optim.Optimizer):
     one more launch sums the squares of all gradients into a device scalar and the AdamW kernel applies
     ``min(1, max_grad_norm / (norm + 1e-6))`` while it reads the gradients (``.grad`` itself is left as it is; a Trainer
     driving this optimizer sets its own ``max_grad_norm`` to 0).  ``last_grad_norm()`` returns the un-clipped norm of the
-    last step as a device tensor (no host sync unless the caller reads it)."""
+    last step as a device tensor (no host sync unless the caller reads it).
+
+    ``emit_into`` (a module, None = off): the step also writes the working-precision copies of the weights.  Every
+    ``WeightCache`` under that module lists its declarative entries (casts, row stacks of casts, concatenated bias vectors);
+    for each entry ALL of whose sources are updated by this step, the kernel stores the new value into the entry's buffer while
+    it is in a register (``peneo_adamw_step_emit``) and the entry is stamped current, so the next forward finds it instead of
+    re-casting 85 M parameters in a second pass.  Entries come into being lazily as before (the first forward builds them,
+    emission starts with the first step after that); an entry with a frozen or gradient-less source, the packed / quantised
+    forms and ``dec.ab`` stay lazy; a buffer that a lazy rebuild re-allocated (after a foreign ``.data`` write, a
+    ``load_state_dict``, a change of compute dtype) is picked up by the next step.  In-place rule: the working copies are
+    OVERWRITTEN by ``step()``, they are not fresh tensors -- a backward must not run after a ``step()`` that followed its
+    forward (it would multiply by the new weights)."""
 
     def __init__(self, params: Iterable, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
-                 max_grad_norm: float = None):
+                 max_grad_norm: float = None, emit_into: nn.Module = None):
+        if emit_into is not None and not isinstance(emit_into, nn.Module):
+            raise TypeError(f"emit_into must be a torch.nn.Module (the model whose weight caches are written), not {type(emit_into).__name__}")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         if max_grad_norm is not None and not max_grad_norm > 0:
             raise ValueError("max_grad_norm must be positive (None switches clipping off)")
         self.max_grad_norm = max_grad_norm
+        self._emit_into = emit_into
+        self._emit, self._emit_plan, self._emitted = None, None, ()
         self._sqnorm = None
         self._tables = None
         self._step = 0
@@ -90,6 +106,8 @@ class FusedAdamW(torch.optim.Optimizer):
         super().__setstate__(state)
         self._tables, self._entries, self._offsets = None, [], []
         self._step = getattr(self, "_step", 0)
+        self._emit_into = getattr(self, "_emit_into", None)
+        self._emit, self._emit_plan, self._emitted = None, None, ()
 
     def _wanted(self):
         return [(p, gi) for gi, group in enumerate(self.param_groups) for p in group["params"] if p.grad is not None]
@@ -126,6 +144,8 @@ class FusedAdamW(torch.optim.Optimizer):
         self._host = (hip.AdamwTensor * len(entries))()
         self._table = torch.empty(C.sizeof(self._host), dtype=torch.uint8, device=dev)
         self._grads = [None] * len(entries)
+        self._emit = ops.AdamwEmitTable([e[0] for e in entries]) if self._emit_into is not None else None
+        self._emit_plan = None
         self._tables = True
 
     def _refresh(self):
@@ -146,6 +166,32 @@ class FusedAdamW(torch.optim.Optimizer):
         if dirty:   # pointer / lr table changed (new .grad tensors, scheduler step): one small H2D copy
             src = torch.frombuffer(memoryview(self._host).cast("B"), dtype=torch.uint8)
             self._table.copy_(src, non_blocking=False)
+            if self._emit is not None and self._emit.reindex():
+                self._emit_plan = None
+
+    def emitted_keys(self):
+        """[(weight cache, key)] of the entries the last step wrote (empty without ``emit_into``)."""
+        return list(self._emitted)
+
+    def _collect_emissions(self):
+        """The declarative cache entries under the model whose sources are ALL tensors of this step -> the emission table
+        (same dirty check and single H2D copy as the tensor table); returns [(cache, key)] to stamp after the launch."""
+        plan = self._emit_plan
+        if plan is not None and all(wc.gen == gen and wc._touched == touched for wc, gen, touched in plan[0]):
+            return plan[1]       # the steady state of a training loop: same entries, same buffers, same parameters as last step
+        index, pairs, emitted, caches = self._emit.index, [], [], []
+        for mod in self._emit_into.modules():
+            wc = getattr(mod, "weight_cache", None)
+            if not isinstance(wc, WeightCache) or any(wc is c[0] for c in caches):
+                continue
+            caches.append((wc, wc.gen, set(wc._touched)))
+            for key, srcs, views in wc.declarative():
+                if all((p.data_ptr(), p.numel()) in index for p in srcs):
+                    pairs += zip(srcs, views)
+                    emitted.append((wc, key))
+        self._emit.update(pairs)
+        self._emit_plan = (caches, emitted)
+        return emitted
 
     def last_grad_norm(self):
         """Global L2 norm of the gradients the last step saw (before clipping); None without max_grad_norm."""
@@ -170,8 +216,17 @@ class FusedAdamW(torch.optim.Optimizer):
             sq = self._sqnorm
             check(lib().peneo_grad_sqnorm(ptr(self._table), ptr(self._chunk_t), ptr(self._chunk_i), self._chunk_t.numel(),
                                           ptr(sq), stream()), "peneo_grad_sqnorm")
-        check(lib().peneo_adamw_step_clip(ptr(self._table), ptr(self._chunk_t), ptr(self._chunk_i), self._chunk_t.numel(),
-                                          float(g0["betas"][0]), float(g0["betas"][1]), float(g0["eps"]), self._step,
-                                          ptr(sq), float(self.max_grad_norm or 0.0), stream()), "peneo_adamw_step_clip")
-        bump_param_epoch()   # the parameters changed in place behind torch's version counters: invalidate the working copies
+        if self._emit is None:
+            check(lib().peneo_adamw_step_clip(ptr(self._table), ptr(self._chunk_t), ptr(self._chunk_i), self._chunk_t.numel(),
+                                              float(g0["betas"][0]), float(g0["betas"][1]), float(g0["eps"]), self._step,
+                                              ptr(sq), float(self.max_grad_norm or 0.0), stream()), "peneo_adamw_step_clip")
+            bump_param_epoch()   # the parameters changed in place behind torch's version counters: invalidate the working copies
+            return loss
+        emitted = self._collect_emissions()
+        ops.adamw_step_emit(self._table, self._chunk_t, self._chunk_i, float(g0["betas"][0]), float(g0["betas"][1]), float(g0["eps"]),
+                            self._step, self._emit, sqnorm=sq, max_grad_norm=float(self.max_grad_norm or 0.0))
+        bump_param_epoch()   # every working copy is stale now ...
+        for wc, key in emitted:                      # ... except those this launch has just written
+            wc.mark_current(key)
+        self._emitted = emitted
         return loss
