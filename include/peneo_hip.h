@@ -817,6 +817,54 @@ void peneo_gemm_set_sk_mode(int mode);
 void peneo_gemm_sk_set_prof(void* stamps);
 void peneo_gemm_sk_set_max_groups(int n);
 
+/* ---- deterministic mode: bit-reproducible training steps ----------------------------------------------------------------
+ * Process-wide like the switches above: a plain global, set while no call of this library is in flight on any thread.
+ *   0  off (default): every launcher picks the kernels it always picked.
+ *   1  every launcher that has an order-independent form uses it; the others run as before.
+ *   2  strict: 1, and a call that would still take an order-dependent accumulation path (same-address float atomics from many
+ *      workgroups) returns PENEO_ERR_INVALID, nothing launched, with a peneo_last_error() message that names the entry point.
+ * PENEO_DETERMINISTIC = 0 / 1 / 2 sets the initial value.  Under modes 1 and 2 two executions of the same calls on the same inputs,
+ * in one process on one device, give the same bits.  Nothing is claimed across devices, processes, ranks, batch sizes or builds.
+ * Forms: peneo_colsum, peneo_layernorm_bwd and peneo_embed_text_bwd switch to single-writer kernels inside their
+ * launchers (no workspace; peneo_encoder_layer_bwd follows through them); peneo_pair_bwd_fused / peneo_pair_bwd_saved give every
+ * workgroup a workspace row of its own, and so does peneo_pair_dz_fused; peneo_pair_x_bwd runs one workgroup per row; the
+ * relative-position tables and the gradient norm take a workspace through the _ws entry points below.  Order-dependent in every
+ * mode (counted; refused under 2): peneo_gemm with a_colsum or pair_dz, peneo_attn_bwd with dq_accum, peneo_ohem_ce,
+ * peneo_weighted_ce, peneo_relpos_bias_bwd(_layers) and peneo_grad_sqnorm without workspace.
+ * peneo_order_dependent_launches: how many calls of this process took an order-dependent accumulation path, in any mode (a result
+ * cannot tell which kernel ran: the tests read this as proof of routing). */
+void peneo_set_deterministic(int mode);
+int peneo_deterministic(void);
+uint64_t peneo_order_dependent_launches(void);
+/* Workspace rows of peneo_pair_bwd_fused / peneo_pair_bwd_saved under the mode in force: [rows][4 * num_heads * D] fp32, zeroed by
+ * the caller, summed afterwards with peneo_colsum.  Mode 0: 256.  Modes 1 / 2: one row per workgroup of the launch, B * (blocks of
+ * the pair triangle) = B * peneo_pair_bwd_rows(N) / 128 - at 8 x 511 tokens 8 448 rows x 4 * 5 * 384 floats = 260 MB.  Size the
+ * workspace under the mode the call runs with. */
+int64_t peneo_pair_bwd_workspace_rows(int B, int N);
+/* The same for peneo_pair_dz_fused (the chunked decoder backward, widths without the fused kernel): rows of its workspace for
+ * launches of up to `npairs` pairs.  Mode 0: 256.  Modes 1 / 2: one row per workgroup of a launch (npairs / 256, at least 256); the
+ * launches of a backward add into the rows one after the other on one stream.  peneo_pair_x_bwd runs one workgroup per row /
+ * column of the triangle under the mode (no workspace). */
+int64_t peneo_pair_dz_fused_workspace_rows(int64_t npairs);
+/* peneo_relpos_bias_bwd_layers / peneo_relpos_bias_bwd with the deterministic fold: under modes 1 / 2 the per-workgroup bin sums go
+ * to 64-bit fixed-point accumulators in `workspace` (2^-32 units, |sum of a bin over the launch| < 2^31) with integer atomics, and
+ * one more launch adds every bin to dw1 / dwx / dwy.  workspace: peneo_relpos_bwd_workspace_bytes(nh, bins1, bins2) bytes (0 under
+ * mode 0, where the calls equal the plain ones and workspace may be NULL), 8-byte aligned, cleared inside, one call at a time. */
+size_t peneo_relpos_bwd_workspace_bytes(int nh, int bins1, int bins2);
+int peneo_relpos_bias_bwd_layers_ws(const void* ds, int L, int64_t layer_stride, const uint8_t* bk1_t, const uint8_t* bkx_t,
+                                    const uint8_t* bky_t, float* dw1, int bins1, float* dwx, float* dwy, int bins2, float scale,
+                                    int B, int nh, int T, int Tp, void* workspace, size_t workspace_bytes, peneo_stream_t stream);
+int peneo_relpos_bias_bwd_ws(const float* g, int64_t ldg, const uint8_t* bk1, const uint8_t* bkx, const uint8_t* bky, float* dw1,
+                             int bins1, float* dwx, float* dwy, int bins2, float scale, int B, int nh, int T, void* workspace,
+                             size_t workspace_bytes, peneo_stream_t stream);
+/* peneo_grad_sqnorm with the deterministic sum: under modes 1 / 2 every chunk's sum is stored to `workspace` and one workgroup
+ * adds them in chunk order; the total lands in slot 0 of sqnorm_dev and the other slots are cleared, so peneo_adamw_step_clip /
+ * _emit read it unchanged.  workspace: peneo_grad_sqnorm_workspace_bytes(n_chunks) bytes (0 under mode 0: the plain call),
+ * 8-byte aligned. */
+size_t peneo_grad_sqnorm_workspace_bytes(int n_chunks);
+int peneo_grad_sqnorm_ws(const peneo_adamw_tensor* table_dev, const int32_t* chunk_tensor_dev, const int32_t* chunk_index_dev,
+                         int n_chunks, double* sqnorm_dev, void* workspace, size_t workspace_bytes, peneo_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

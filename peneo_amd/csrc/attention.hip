@@ -1485,6 +1485,8 @@ extern "C" int peneo_attn_bwd(int dtype, const void* q, const void* k, const voi
   PENEO_REQUIRE(!ds_out || (reinterpret_cast<uintptr_t>(ds_out) & 15) == 0, "peneo_attn_bwd: ds_out must be 16-byte aligned");
   PENEO_REQUIRE(ld_qkv >= (int64_t)nh * d && ld_out >= (int64_t)nh * d && ld_dqkv >= (int64_t)nh * d, "peneo_attn_bwd: leading dims too small");
   PENEO_REQUIRE(!g_bias || bias, "peneo_attn_bwd: g_bias needs bias (it shares its row stride)");
+  // dQ through fp32 atomics from every key block's workgroup (g_bias: one add per address and launch, order-independent)
+  if (dq_accum) PENEO_ORDER_DEPENDENT("peneo_attn_bwd");
   AttnParams p = {};
   p.q = q; p.k = k; p.v = v; p.ld = ld_qkv; p.kt = kt; p.qt = qt; p.dot = dot; p.B = B; p.nh = nh; p.T = T; p.d = d;
   p.Tp = peneo_attn_padded_len(T); p.scale = scale; p.bias = bias; p.bias_ld = bias_ld; p.key_bias = key_bias;

@@ -18,6 +18,18 @@ constexpr int kWave = 64;
 void set_error(const char* fmt, ...);
 int check_launch(const char* what);
 
+// deterministic mode (api.hip; peneo_set_deterministic): 0 off, 1 every launcher that has an order-independent form uses it,
+// 2 = 1 and a call that would still take an order-dependent accumulation path is refused
+int det_mode();
+// called by a launcher that is about to take an order-dependent accumulation path (same-address float atomics from many
+// workgroups): counts the call (peneo_order_dependent_launches); under mode 2 sets the error and returns PENEO_ERR_INVALID
+int order_dependent(const char* entry_point);
+#define PENEO_ORDER_DEPENDENT(entry_point)                        \
+  do {                                                            \
+    const int od_rc_ = ::peneo::order_dependent(entry_point);     \
+    if (od_rc_ != PENEO_OK) return od_rc_;                        \
+  } while (0)
+
 #define PENEO_REQUIRE(cond, ...)                \
   do {                                          \
     if (!(cond)) {                              \

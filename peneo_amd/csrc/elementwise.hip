@@ -205,6 +205,80 @@ __global__ __launch_bounds__(256) void colsum_vec_kernel(const T* x, int64_t ldx
   }
 }
 
+// Deterministic form (peneo_set_deterministic): single writer, no workspace.  A workgroup owns DCS_COLS columns and walks ALL
+// rows: row lane rl sums rows rl, rl + RL, ... in index order; the lanes' sums meet in LDS, where 256 / DCS_COLS threads per column
+// each add RL * DCS_COLS / 256 consecutive lanes in lane order and one thread adds those in order.  The result is one fixed
+// expression of the inputs, whatever the scheduler does.  CPT = 8: a thread owns 8 consecutive columns (the vector form's 16-byte
+// loads), CPT = 1: one column.  The grid is N / 16 workgroups (192 at N = 3072, 48 at N = 768), so a launch is bound by the
+// latency of rows / RL dependent-free loads per thread, not by bandwidth: DESIGN 25 has the measured cost.
+constexpr int DCS_COLS = 16;
+template <typename T, int CPT>
+__global__ __launch_bounds__(256) void colsum_det_kernel(const T* x, int64_t ldx, int64_t M, int64_t N, float* out, int accumulate) {
+  constexpr int CG = DCS_COLS / CPT, RL = 256 / CG, GR = 256 / DCS_COLS, PER = RL / GR;
+  __shared__ float part[RL][DCS_COLS + 1];
+  __shared__ float part2[GR][DCS_COLS + 1];
+  const int cg = threadIdx.x % CG, rl = threadIdx.x / CG;
+  const int64_t n = (int64_t)blockIdx.x * DCS_COLS + cg * CPT;
+  float acc[CPT];
+#pragma unroll
+  for (int e = 0; e < CPT; ++e) acc[e] = 0.f;
+  if (n < N) {
+    constexpr int U = 8;               // rows in flight per thread
+    for (int64_t m0 = rl; m0 < M; m0 += (int64_t)RL * U) {
+      if constexpr (CPT == 8 && sizeof(T) == 2) {
+        uint4 v[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const int64_t m = m0 + (int64_t)u * RL;
+          v[u] = m < M ? *reinterpret_cast<const uint4*>(x + m * ldx + n) : make_uint4(0, 0, 0, 0);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          float f[8];
+          unpack16<T>(v[u], f);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) acc[e] += f[e];
+        }
+      } else {
+        float v[U][CPT];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const int64_t m = m0 + (int64_t)u * RL;
+#pragma unroll
+          for (int e = 0; e < CPT; e += (CPT == 8 ? 4 : 1)) {
+            if constexpr (CPT == 8) {
+              const float4 t = m < M ? *reinterpret_cast<const float4*>(x + m * ldx + n + e) : make_float4(0.f, 0.f, 0.f, 0.f);
+              v[u][e] = t.x; v[u][e + 1] = t.y; v[u][e + 2] = t.z; v[u][e + 3] = t.w;
+            } else {
+              v[u][e] = m < M ? Elem<T>::load(x + m * ldx + n) : 0.f;
+            }
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+          for (int e = 0; e < CPT; ++e) acc[e] += v[u][e];
+      }
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < CPT; ++e) part[rl][cg * CPT + e] = acc[e];
+  __syncthreads();
+  const int c = threadIdx.x % DCS_COLS, gr = threadIdx.x / DCS_COLS;
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < PER; ++i) s += part[gr * PER + i][c];
+  part2[gr][c] = s;
+  __syncthreads();
+  const int64_t nc = (int64_t)blockIdx.x * DCS_COLS + threadIdx.x;
+  if (threadIdx.x < DCS_COLS && nc < N) {
+    float sum = 0.f;
+#pragma unroll
+    for (int g = 0; g < GR; ++g) sum += part2[g][threadIdx.x];
+    out[nc] = accumulate ? out[nc] + sum : sum;
+  }
+}
+
 // fused multi-tensor AdamW (decoupled weight decay, torch.optim.AdamW arithmetic): one launch for every parameter of
 // every group; block = one 4096-element chunk of one tensor, per-tensor lr / weight decay from the table
 constexpr int ADAMW_CHUNK = 4096;
@@ -284,6 +358,8 @@ __global__ __launch_bounds__(256) void adamw_kernel(const peneo_adamw_tensor* ta
 }
 
 // sum of squares of every gradient of the table (same chunk maps): per-block fp32 tree, one fp64 atomic per block
+// PARTIAL (deterministic mode): the block's sum goes to out[blockIdx.x] with a plain store; grad_sqnorm_fold_kernel adds the rows
+template <bool PARTIAL>
 __global__ __launch_bounds__(256) void grad_sqnorm_kernel(const peneo_adamw_tensor* tab, const int32_t* chunk_tensor,
                                                           const int32_t* chunk_index, double* out) {
   const peneo_adamw_tensor t = tab[chunk_tensor[blockIdx.x]];
@@ -303,7 +379,26 @@ __global__ __launch_bounds__(256) void grad_sqnorm_kernel(const peneo_adamw_tens
   acc = wave_sum(acc);
   if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
   __syncthreads();
-  if (threadIdx.x == 0) atomicAdd(out + (blockIdx.x % GRAD_SQNORM_SLOTS), (double)part[0] + (double)part[1] + (double)part[2] + (double)part[3]);
+  if (threadIdx.x == 0) {
+    const double sum = (double)part[0] + (double)part[1] + (double)part[2] + (double)part[3];
+    if constexpr (PARTIAL) out[blockIdx.x] = sum; else atomicAdd(out + (blockIdx.x % GRAD_SQNORM_SLOTS), sum);
+  }
+}
+
+// one workgroup: thread t adds partials t, t + 256, ... in index order, the 256 sums are added in thread order; the total goes to
+// slot 0 and the other slots are cleared, so adamw_kernel's sum over the slots reads the same bits every time
+__global__ __launch_bounds__(256) void grad_sqnorm_fold_kernel(const double* partials, int n, double* out) {
+  __shared__ double part[256];
+  double s = 0.0;
+  for (int i = threadIdx.x; i < n; i += 256) s += partials[i];
+  part[threadIdx.x] = s;
+  __syncthreads();
+  if (threadIdx.x < GRAD_SQNORM_SLOTS) {
+    double total = 0.0;
+    if (threadIdx.x == 0)
+      for (int i = 0; i < 256; ++i) total += part[i];
+    out[threadIdx.x] = total;
+  }
 }
 
 // Many fp32 -> bf16 casts in ONE launch (the working-precision copies of a model's weights after an optimizer step): block =
@@ -344,10 +439,29 @@ extern "C" int peneo_grad_sqnorm_slots(void) { return GRAD_SQNORM_SLOTS; }
 extern "C" int peneo_grad_sqnorm(const peneo_adamw_tensor* table_dev, const int32_t* chunk_tensor_dev, const int32_t* chunk_index_dev,
                                  int n_chunks, double* sqnorm_dev, peneo_stream_t stream) {
   PENEO_REQUIRE(table_dev && chunk_tensor_dev && chunk_index_dev && n_chunks > 0 && sqnorm_dev, "peneo_grad_sqnorm: bad arguments");
+  PENEO_ORDER_DEPENDENT("peneo_grad_sqnorm");
   if (hipMemsetAsync(sqnorm_dev, 0, sizeof(double) * GRAD_SQNORM_SLOTS, (hipStream_t)stream) != hipSuccess) return check_launch("peneo_grad_sqnorm");
-  hipLaunchKernelGGL(grad_sqnorm_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, table_dev, chunk_tensor_dev,
+  hipLaunchKernelGGL(grad_sqnorm_kernel<false>, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, table_dev, chunk_tensor_dev,
                      chunk_index_dev, sqnorm_dev);
   return check_launch("peneo_grad_sqnorm");
+}
+
+extern "C" size_t peneo_grad_sqnorm_workspace_bytes(int n_chunks) {
+  return det_mode() >= 1 && n_chunks > 0 ? sizeof(double) * (size_t)n_chunks : 0;
+}
+
+extern "C" int peneo_grad_sqnorm_ws(const peneo_adamw_tensor* table_dev, const int32_t* chunk_tensor_dev, const int32_t* chunk_index_dev,
+                                    int n_chunks, double* sqnorm_dev, void* workspace, size_t workspace_bytes, peneo_stream_t stream) {
+  if (det_mode() == 0) return peneo_grad_sqnorm(table_dev, chunk_tensor_dev, chunk_index_dev, n_chunks, sqnorm_dev, stream);
+  PENEO_REQUIRE(table_dev && chunk_tensor_dev && chunk_index_dev && n_chunks > 0 && sqnorm_dev, "peneo_grad_sqnorm_ws: bad arguments");
+  PENEO_REQUIRE(workspace && (reinterpret_cast<uintptr_t>(workspace) & 7) == 0 && workspace_bytes >= peneo_grad_sqnorm_workspace_bytes(n_chunks),
+                "peneo_grad_sqnorm_ws: workspace of %zu bytes, 8-byte aligned, needed under the deterministic mode (got %zu)",
+                peneo_grad_sqnorm_workspace_bytes(n_chunks), workspace_bytes);
+  double* partials = reinterpret_cast<double*>(workspace);
+  hipLaunchKernelGGL(grad_sqnorm_kernel<true>, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, table_dev, chunk_tensor_dev,
+                     chunk_index_dev, partials);
+  hipLaunchKernelGGL(grad_sqnorm_fold_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, n_chunks, sqnorm_dev);
+  return check_launch("peneo_grad_sqnorm_ws");
 }
 
 extern "C" int peneo_adamw_step_clip(const peneo_adamw_tensor* table_dev, const int32_t* chunk_tensor_dev, const int32_t* chunk_index_dev,
@@ -461,11 +575,21 @@ extern "C" int peneo_colsum(int dtype, const void* x, int64_t ldx, int64_t M, in
   PENEO_REQUIRE(ok_dt(dtype), "peneo_colsum: bad dtype");
   PENEO_REQUIRE(x && out && M > 0 && N > 0 && ldx >= N, "peneo_colsum: bad arguments");
   hipStream_t st = (hipStream_t)stream;
+  const int esz = dtype == PENEO_BF16 ? 2 : 4;
+  const bool vec = (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (ldx * esz) % 16 == 0 && N % 8 == 0;
+  if (det_mode() >= 1) {   // single-writer kernels: out is written once per column, no memset
+    dim3 dgrid((unsigned)((N + DCS_COLS - 1) / DCS_COLS));
+    if (vec && dtype == PENEO_BF16) hipLaunchKernelGGL((colsum_det_kernel<bf16_t, 8>), dgrid, dim3(256), 0, st, (const bf16_t*)x, ldx, M, N, out, accumulate);
+    else if (vec) hipLaunchKernelGGL((colsum_det_kernel<float, 8>), dgrid, dim3(256), 0, st, (const float*)x, ldx, M, N, out, accumulate);
+    else if (dtype == PENEO_BF16) hipLaunchKernelGGL((colsum_det_kernel<bf16_t, 1>), dgrid, dim3(256), 0, st, (const bf16_t*)x, ldx, M, N, out, accumulate);
+    else hipLaunchKernelGGL((colsum_det_kernel<float, 1>), dgrid, dim3(256), 0, st, (const float*)x, ldx, M, N, out, accumulate);
+    return check_launch("peneo_colsum");
+  }
+  PENEO_ORDER_DEPENDENT("peneo_colsum");
   if (!accumulate) {
     if (hipMemsetAsync(out, 0, sizeof(float) * N, st) != hipSuccess) { set_error("peneo_colsum: memset failed"); return PENEO_ERR_LAUNCH; }
   }
-  const int esz = dtype == PENEO_BF16 ? 2 : 4;
-  if ((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (ldx * esz) % 16 == 0 && N % 8 == 0) {
+  if (vec) {
     dim3 vgrid((unsigned)((N + 255) / 256), (unsigned)((M + CSV_ROWS - 1) / CSV_ROWS));
     if (dtype == PENEO_BF16)
       hipLaunchKernelGGL(colsum_vec_kernel<bf16_t>, vgrid, dim3(256), 0, st, (const bf16_t*)x, ldx, M, N, out);

@@ -177,6 +177,106 @@ __global__ __launch_bounds__(256) void embed_box_bwd_kernel(const T* d_out, int6
   }
 }
 
+// ---- deterministic form of both kernels above (peneo_set_deterministic): single writer, no workspace ----
+// A destination is one row of one table: (word, id), (pos, position id), (x, v) - fed by the left AND the right coordinate, columns
+// 0.. and 2 cs.. of d_out - (y, v) likewise from top and bottom, (h, v), (w, v).  Workgroup = one token r.  For every destination its
+// token feeds, the workgroup walks ALL tokens in chunks of 256 (one token per thread: does it feed the destination, through which
+// field; wave ballots to LDS).  If a token in front of r feeds it, r is not the destination's first token and moves on; the first
+// token adds the d_out rows of every feeding token in index order (field 0 in front of field 1 inside a 64-token group) and does the
+// one read-modify-write of the table row.  Narrow tables (coordinates, shapes: <= 128 columns) split the matches over 256 / CL row
+// lanes round-robin and add the lanes' sums in lane order.
+struct EmbDetArgs {
+  const int64_t* ids; const int32_t* pos_ids; const int64_t* bbox;
+  peneo_embed_grads g;
+  int cs, ss, max_2d, clip_hw, H;
+  int64_t pad;
+};
+// index of token r in field f (0 / 1) of table tb (0 word, 1 pos, 2 x, 3 y, 4 h, 5 w); -1: none (pad id, invalid box, no such field)
+__device__ __forceinline__ int64_t emb_field(const EmbDetArgs& a, int tb, int f, int64_t r) {
+  if (tb < 2) {
+    if (f) return -1;
+    const int64_t v = tb == 0 ? a.ids[r] : (int64_t)a.pos_ids[r];
+    return v == a.pad ? -1 : v;
+  }
+  const SpatialIdx sp = spatial_idx(a.bbox + r * 4, a.max_2d, a.clip_hw);
+  if (!sp.ok) return -1;
+  switch (tb) {
+    case 2: return f ? sp.r : sp.l;
+    case 3: return f ? sp.b : sp.t;
+    case 4: return f ? -1 : sp.h;
+    default: return f ? -1 : sp.w;
+  }
+}
+template <typename T>
+__global__ __launch_bounds__(256) void embed_bwd_det_kernel(const T* d_out, int64_t rpb, int64_t bstride, EmbDetArgs a, int64_t rows) {
+  __shared__ unsigned long long smask[2][4];
+  __shared__ float part[256];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int64_t r = blockIdx.x;
+  for (int tb = 0; tb < 6; ++tb) {
+    float* tab = tb == 0 ? a.g.word : tb == 1 ? a.g.pos : tb == 2 ? a.g.x : tb == 3 ? a.g.y : tb == 4 ? a.g.h : a.g.w;
+    if (!tab) continue;
+    const int W = tb < 2 ? a.H : (tb < 4 ? a.cs : a.ss);
+    const int col0[2] = {tb < 2 ? 0 : tb == 2 ? 0 : tb == 3 ? a.cs : tb == 4 ? 4 * a.cs : 4 * a.cs + a.ss,
+                         tb == 2 ? 2 * a.cs : 3 * a.cs};
+    int CL = 256;
+    while (CL / 2 >= W && CL > 1) CL >>= 1;                     // smallest power of two >= W, at most 256
+    const int RL = 256 / CL, cl = tid % CL, rl = tid / CL;
+    for (int f0 = 0; f0 < 2; ++f0) {
+      const int64_t v = emb_field(a, tb, f0, r);
+      if (v < 0) continue;
+      if (f0 == 1 && v == emb_field(a, tb, 0, r)) continue;      // the same destination: handled with field 0
+      float acc[4] = {0.f, 0.f, 0.f, 0.f};
+      int k = 0;
+      bool first = true;
+      for (int64_t cb = 0; cb < rows; cb += 256) {
+        const int64_t rr = cb + tid;
+        bool m0 = false, m1 = false;
+        if (rr < rows) { m0 = emb_field(a, tb, 0, rr) == v; m1 = emb_field(a, tb, 1, rr) == v; }
+        const unsigned long long b0 = __ballot(m0), b1 = __ballot(m1);
+        if (lane == 0) { smask[0][wave] = b0; smask[1][wave] = b1; }
+        if (__syncthreads_or((m0 || m1) && rr < r)) { first = false; break; }   // (block-uniform)
+        for (int w = 0; w < 4; ++w)
+          for (int f = 0; f < 2; ++f) {
+            unsigned long long mk = smask[f][w];
+            while (mk) {
+              const int bit = __ffsll(mk) - 1;
+              mk &= mk - 1;
+              if ((k & (RL - 1)) == rl) {
+                const T* d = d_out + row_off(cb + w * 64 + bit, rpb, bstride, a.H) + col0[f];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                  const int c = cl + q * CL;
+                  if (c < W) acc[q] += Elem<T>::load(d + c);
+                }
+              }
+              ++k;
+            }
+          }
+        __syncthreads();                                          // smask is rewritten by the next chunk
+      }
+      if (!first) continue;
+      if (RL > 1) {                                               // (W <= CL <= 128: one column per thread)
+        part[rl * CL + cl] = acc[0];
+        __syncthreads();
+        if (rl == 0) {
+          float s = 0.f;
+          for (int j = 0; j < RL; ++j) s += part[j * CL + cl];
+          acc[0] = s;
+        }
+        __syncthreads();
+      }
+      if (rl == 0) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int c = cl + q * CL;
+          if (c < W) tab[v * W + c] += acc[q];
+        }
+      }
+    }
+  }
+}
+
 // ---- patches: [B, C, Hi, Wi] -> [B * gh * gw, C*256], k = c*256 + py*16 + px (conv weight order) ----
 template <typename T>
 __global__ void im2col_kernel(const float* img, int B, int Cc, int Hi, int Wi, T* out) {
@@ -268,6 +368,22 @@ extern "C" int peneo_embed_text_bwd(int dtype, const void* d_out, int64_t rpb, i
   if (g->word) PENEO_REQUIRE(input_ids && pos_ids && g->pos, "peneo_embed_text_bwd: text grads incomplete");
   if (g->x) PENEO_REQUIRE(bbox && g->y && g->h && g->w, "peneo_embed_text_bwd: spatial grads incomplete");
   int64_t rows = (int64_t)B * S;
+  if (det_mode() >= 1 && H <= 1024 && (!g->x || (H == 4 * coord_size + 2 * shape_size && coord_size > 0 && shape_size > 0))) {
+    if (!g->word && !g->x) return PENEO_OK;
+    EmbDetArgs a;
+    a.ids = input_ids; a.pos_ids = pos_ids; a.bbox = bbox; a.g = *g;
+    if (!g->word) a.g.pos = nullptr;                                   // (as the kernels above: the text tables come together,
+    if (!g->x) a.g.y = a.g.h = a.g.w = nullptr;                        //  and so do the box tables)
+    a.cs = coord_size; a.ss = shape_size; a.max_2d = max_2d; a.clip_hw = clip_hw; a.H = H; a.pad = pad_id;
+    if (dtype == PENEO_BF16)
+      hipLaunchKernelGGL(embed_bwd_det_kernel<bf16_t>, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)d_out, rpb,
+                         bstride, a, rows);
+    else
+      hipLaunchKernelGGL(embed_bwd_det_kernel<float>, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, (const float*)d_out, rpb,
+                         bstride, a, rows);
+    return check_launch("peneo_embed_text_bwd");
+  }
+  PENEO_ORDER_DEPENDENT("peneo_embed_text_bwd");
   dim3 grid((unsigned)((rows + 3) / 4));
   peneo_embed_grads rest = *g;
   const size_t box_lds = (size_t)EBX_TOK * H * sizeof(float);

@@ -993,6 +993,8 @@ extern "C" int peneo_gemm(int dtype, int a_kmajor, int b_kmajor, int M, int N, i
   PENEO_REQUIRE(!p.ep.a_colsum || !a_kmajor, "peneo_gemm: a_colsum needs A as [K, M] (a_kmajor = 0)");
   bool cs_fused = false;
   PENEO_REQUIRE(p.ep.drop_p >= 0.f && p.ep.drop_p < 1.f, "peneo_gemm: drop_p out of range");
+  // the two epilogues that add into shared fp32 addresses from many workgroups (a_colsum, the pair_dz workspace rows)
+  if (p.ep.a_colsum || p.ep.pair_dz) PENEO_ORDER_DEPENDENT("peneo_gemm");
   const int KT = dtype == PENEO_BF16 ? 64 : 32;
   const int ktiles = (K + KT - 1) / KT;
   if (split_k < 1) split_k = 1;

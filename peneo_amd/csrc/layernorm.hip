@@ -379,6 +379,87 @@ __global__ __launch_bounds__(256) void ln_bwd32_kernel(const T* dy, LnMap dym, c
   }
 }
 
+// Deterministic form of the parameter gradients (peneo_set_deterministic): the row kernels above run without dgamma / dbeta / dcol
+// (dx and dx2 are single-writer already), then this kernel sums the columns with one writer per column: a workgroup owns 16 columns
+// and walks ALL rows, row lane rl taking rows rl, rl + RL, ... in index order; the lanes' sums meet in LDS and are added in lane order
+// (colsum_det_kernel's scheme, elementwise.hip).  dgamma / dbeta repeat the row kernels' arithmetic per element (the same dropout
+// mask, (x - mean) * rstd); dcol sums the STORED dx2 (dx without it), i.e. what peneo_colsum of that tensor gives.
+template <typename T>
+__global__ __launch_bounds__(256) void ln_pgrad_det_kernel(const T* dy, LnMap dym, const T* x, LnMap xm, const float* mean,
+                                                           const float* rstd, float* dgamma, float* dbeta, int64_t rows, int H,
+                                                           float drop_p, uint32_t seed, const T* dsrc, LnMap dsm, float* dcol) {
+  constexpr int VEC = Elem<T>::kVec, NC = 16, CG = NC / VEC, RL = 256 / CG, GR = 256 / NC, PER = RL / GR;
+  __shared__ float part[3][RL][NC + 1];
+  __shared__ float part2[3][GR][NC + 1];
+  const int cg = threadIdx.x % CG, rl = threadIdx.x / CG;
+  const int c0 = blockIdx.x * NC + cg * VEC;
+  const uint32_t thresh = (uint32_t)fminf(drop_p * 4294967296.0f, 4294967040.0f);
+  const float keep_scale = drop_p > 0.f ? 1.0f / (1.0f - drop_p) : 1.0f;
+  float ag[VEC], ab[VEC], ac[VEC];
+#pragma unroll
+  for (int e = 0; e < VEC; ++e) { ag[e] = 0.f; ab[e] = 0.f; ac[e] = 0.f; }
+  const bool pg = dgamma != nullptr || dbeta != nullptr;
+  if (c0 < H) {
+    constexpr int U = 4;   // rows in flight per thread
+    for (int64_t r0 = rl; r0 < rows; r0 += (int64_t)RL * U) {
+      uint4 vd[U], vx[U], vs[U];
+      float mu[U], rs[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int64_t r = r0 + (int64_t)u * RL;
+        const bool in = r < rows;
+        const uint4 z = make_uint4(0, 0, 0, 0);
+        vd[u] = (in && pg) ? *reinterpret_cast<const uint4*>(dy + ln_row_off(r, dym, H) + c0) : z;
+        vx[u] = (in && pg) ? *reinterpret_cast<const uint4*>(x + ln_row_off(r, xm, H) + c0) : z;
+        vs[u] = (in && dcol) ? *reinterpret_cast<const uint4*>(dsrc + ln_row_off(r, dsm, H) + c0) : z;
+        mu[u] = (in && pg) ? mean[r] : 0.f;
+        rs[u] = (in && pg) ? rstd[r] : 0.f;
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int64_t r = r0 + (int64_t)u * RL;
+        if (r >= rows) continue;
+        float d[VEC], xv[VEC], sv[VEC];
+        unpack16<T>(vd[u], d);
+        unpack16<T>(vx[u], xv);
+        unpack16<T>(vs[u], sv);
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+          float dd = d[e];
+          if (drop_p > 0.f) dd = dropout_keep(seed, (uint64_t)r * H + c0 + e, thresh) ? dd * keep_scale : 0.f;
+          const float h = (xv[e] - mu[u]) * rs[u];
+          ag[e] += dd * h;
+          ab[e] += dd;
+          ac[e] += sv[e];
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < VEC; ++e) { part[0][rl][cg * VEC + e] = ag[e]; part[1][rl][cg * VEC + e] = ab[e]; part[2][rl][cg * VEC + e] = ac[e]; }
+  __syncthreads();
+  const int c = threadIdx.x % NC, gr = threadIdx.x / NC;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < PER; ++i) s += part[k][gr * PER + i][c];
+    part2[k][gr][c] = s;
+  }
+  __syncthreads();
+  const int col = blockIdx.x * NC + threadIdx.x;
+  if (threadIdx.x < NC && col < H) {
+    float s[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+#pragma unroll
+      for (int g = 0; g < GR; ++g) s[k] += part2[k][g][threadIdx.x];
+    if (dgamma) dgamma[col] += s[0];
+    if (dbeta) dbeta[col] += s[1];
+    if (dcol) dcol[col] += s[2];
+  }
+}
+
 template <typename T, int NV, int LW = 32>
 static void launch_ln_fwd32(hipStream_t st, const void* x, LnMap xm, void* y, LnMap ym, const float* gamma, const float* beta,
                             float eps, float* mean, float* rstd, int64_t rows, float drop_p, uint32_t seed) {
@@ -505,8 +586,32 @@ extern "C" int peneo_layernorm_bwd(int dtype, const void* dy, int64_t dy_rpb, in
   LnMap dym{dy_rpb, dy_bstride}, xm{x_rpb, x_bstride}, dxm{dx_rpb, dx_bstride};
   PENEO_REQUIRE(drop_p >= 0.f && drop_p < 1.f && drop2_p >= 0.f && drop2_p < 1.f, "peneo_layernorm_bwd: drop_p out of range");
   PENEO_REQUIRE(!dx_dropped || (reinterpret_cast<uintptr_t>(dx_dropped) & 15) == 0, "peneo_layernorm_bwd: dx_dropped must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  if (dgamma || dbeta || dx_colsum) {
+    if (det_mode() >= 1) {
+      // deterministic form: the single-writer column kernel for dgamma / dbeta FIRST (dx may alias dy), the row kernel without its
+      // column sums, then the column kernel again for the sums of the dx it stored
+      const dim3 pgrid((unsigned)((H + 15) / 16));
+      const LnMap dsm = dx_dropped ? LnMap{0, 0} : dxm;
+      const void* dsrc = dx_dropped ? dx_dropped : dx;
+      auto columns = [&](float* dg, float* db, float* dc) {
+        if (dtype == PENEO_BF16)
+          hipLaunchKernelGGL(ln_pgrad_det_kernel<bf16_t>, pgrid, dim3(256), 0, st, (const bf16_t*)dy, dym, (const bf16_t*)x, xm, mean, rstd,
+                             dg, db, rows, H, drop_p, drop_seed, (const bf16_t*)dsrc, dsm, dc);
+        else
+          hipLaunchKernelGGL(ln_pgrad_det_kernel<float>, pgrid, dim3(256), 0, st, (const float*)dy, dym, (const float*)x, xm, mean, rstd,
+                             dg, db, rows, H, drop_p, drop_seed, (const float*)dsrc, dsm, dc);
+      };
+      if (dgamma || dbeta) columns(dgamma, dbeta, nullptr);
+      rc = peneo_layernorm_bwd(dtype, dy, dy_rpb, dy_bstride, x, x_rpb, x_bstride, dx, dx_rpb, dx_bstride, gamma, mean, rstd, nullptr,
+                               nullptr, rows, H, drop_p, drop_seed, dx_dropped, drop2_p, drop2_seed, nullptr, stream);
+      if (rc) return rc;
+      if (dx_colsum) columns(nullptr, nullptr, dx_colsum);
+      return check_launch("peneo_layernorm_bwd");
+    }
+    PENEO_ORDER_DEPENDENT("peneo_layernorm_bwd");
+  }
   if (ln_aligned(dy, dy_bstride, dtype) && ln_aligned(x, x_bstride, dtype) && ln_aligned(dx, dx_bstride, dtype)) {
-    hipStream_t st = (hipStream_t)stream;
     bool done = dtype == PENEO_BF16
         ? ln32_dispatch<bf16_t>(H, [&](auto nv, auto lw) { launch_ln_bwd32<bf16_t, decltype(nv)::value, decltype(lw)::value>(st, dy, dym, x, xm, dx, dxm, gamma, mean, rstd, dgamma, dbeta, rows, drop_p, drop_seed, dx_dropped, drop2_p, drop2_seed, nullptr, 0, dx_colsum); })
         : ln32_dispatch<float>(H, [&](auto nv, auto lw) { launch_ln_bwd32<float, decltype(nv)::value, decltype(lw)::value>(st, dy, dym, x, xm, dx, dxm, gamma, mean, rstd, dgamma, dbeta, rows, drop_p, drop_seed, dx_dropped, drop2_p, drop2_seed, nullptr, 0, dx_colsum); });

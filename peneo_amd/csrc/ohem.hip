@@ -198,6 +198,7 @@ extern "C" int peneo_ohem_ce(const float* logits, const int64_t* tags, const flo
   PENEO_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "peneo_ohem_ce: workspace must be 256-byte aligned");
   OhemWs w = carve(workspace, n);
   PENEO_REQUIRE(workspace_bytes >= w.total, "peneo_ohem_ce: workspace too small (%zu < %zu)", workspace_bytes, w.total);
+  PENEO_ORDER_DEPENDENT("peneo_ohem_ce");   // ohem_finish_kernel: every workgroup adds into the 32 result words
   hipStream_t st = (hipStream_t)stream;
   const int blocks = (int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
   hipLaunchKernelGGL(ohem_ce_kernel, dim3(blocks), dim3(256), 0, st, logits, tags, class_weight, n, C, w.ce, w.flag, w.key_in, w.val_in);

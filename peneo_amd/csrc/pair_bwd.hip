@@ -67,11 +67,20 @@ struct PairBwdParams {
   bf16_t* dz; bf16_t* x;         // [B][ntiles * 128][nh*D] / [.. ][D]
   const char* act;               // saved-activation form: the forward's records (common.h: PB_REC_BYTES), else NULL
   float* part_a; float* part_b;  // per-block partial sums [B][ntiles][8][D] / [B][ntiles][16][D] fp32
-  float* ws;                     // [PB_SLOTS][4 * nh*D]
+  float* ws;                     // [PB_SLOTS][4 * nh*D]; ws_own: [B * ntiles][4 * nh*D]
   int ntiles;
+  int ws_own;                    // deterministic mode: every workgroup of the launch has a workspace row of its own
   uint32_t drop_thr16, drop_seed; float drop_scale;   // K12 dropout of the forward (0 = off): mask regenerated, never stored
   unsigned long long* dbg;       // optional (tools/): per wave of the first 256 blocks: cycles in the loop, cycles waiting at the top
 };
+
+// Workspace row of this workgroup's dW2 / db1 sums.  By default the documents of a batch and every 256th workgroup share a row, and
+// their atomics meet in arrival order.  ws_own (deterministic mode): one row per workgroup of the launch, so every address receives
+// exactly one add onto the caller's zero - exact - and the rows are summed by the deterministic column sum.  The atomics themselves,
+// their number and their place stay: the counted vector-memory waits of the kernels hold in both modes.
+__device__ __forceinline__ int64_t pb_ws_row(const PairBwdParams& p) {
+  return p.ws_own ? (int64_t)blockIdx.y * p.ntiles + blockIdx.x : (int64_t)(blockIdx.x % PB_SLOTS);
+}
 
 // hand-issued fragment reads (the compiler would wait for every ds_read right in front of its MFMA: with one wave per SIMD
 // nothing else covers that latency).  The reader owns lgkmcnt: pb_lgkm0 waits and ties the fragment registers to the wait.
@@ -315,7 +324,7 @@ __global__ __launch_bounds__(PW_WAVES * 64, 2) void pair_bwd_ws_kernel(PairBwdPa
         }
       }
     }
-    float* slot = p.ws + (int64_t)(blockIdx.x % PB_SLOTS) * 4 * ncol;
+    float* slot = p.ws + pb_ws_row(p) * 4 * ncol;
     auto flush = [&](int s) {
       if (wave == (s & 3) && lane < 32) {
         const float4* src = sPart + (s & 1) * (4 * 32) + lane;
@@ -925,7 +934,7 @@ __global__ __launch_bounds__(PW_WAVES * 64, 2) void pair_bwd_sv_kernel(PairBwdPa
     };
     wrequest(0, 0);
     wrequest(1, 1);
-    float* wslot = p.ws + (int64_t)(blockIdx.x % PB_SLOTS) * 4 * ncol;
+    float* wslot = p.ws + pb_ws_row(p) * 4 * ncol;
     const int t_swz = (r32 >> 2) & 3;
     __syncthreads();                                          // matches the producers' barrier
     int slot = 0;                                             // s % 3
@@ -1038,7 +1047,9 @@ __global__ __launch_bounds__(PW_WAVES * 64, 2) void pair_bwd_sv_kernel(PairBwdPa
   }
 }
 
-template <int KS, bool DROP>
+// OWN: the deterministic mode's workspace row per workgroup as an instantiation of its own - this kernel has no register to spare
+// (256 + 256), and the run-time choice of pb_ws_row cost the default path two more spilled dwords
+template <int KS, bool DROP, bool OWN = false>
 __global__ __launch_bounds__(PB_WAVES * 64, 1) void pair_bwd_one_kernel(PairBwdParams p) {
   using T = bf16_t;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1155,7 +1166,7 @@ __global__ __launch_bounds__(PB_WAVES * 64, 1) void pair_bwd_one_kernel(PairBwdP
     asm volatile("" : "+a"(du[t]));
   }
 
-  float* slot_ws = p.ws + (int64_t)(blockIdx.x % PB_SLOTS) * 4 * ncol;
+  float* slot_ws = p.ws + (OWN ? (int64_t)blockIdx.y * p.ntiles + blockIdx.x : (int64_t)(blockIdx.x % PB_SLOTS)) * 4 * ncol;
   auto flush = [&](int s) {
     if (wave == (s & 3) && lane < 32) {
       const float4* src = sPart + (s & 1) * (4 * 32) + lane;
@@ -1523,18 +1534,18 @@ __global__ __launch_bounds__(PB_WAVES * 64, 1) void pair_bwd_one_kernel(PairBwdP
   }
 }
 
-template <int KS, bool DROP>
+template <int KS, bool DROP, bool OWN>
 static int launch_pair_bwd_one(const PairBwdParams& p, hipStream_t st) {
   const int ncol = p.a.num_heads * p.D;
   size_t sh = (size_t)3 * KS * 1024 + (size_t)ncol * 12 + (size_t)4 * 32 * 16 * 3 + (size_t)2 * 4 * 2048 + (size_t)4 * 32 * 80;
   const size_t red = (size_t)4 * (KS / 2) * 16 * 32 * sizeof(float);
   if (sh < red) sh = red;
   if (sh > 160 * 1024) { set_error("peneo_pair_bwd_fused: D=%d needs %zu bytes of LDS", p.D, sh); return PENEO_ERR_INVALID; }
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(pair_bwd_one_kernel<KS, DROP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh) != hipSuccess) {
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(pair_bwd_one_kernel<KS, DROP, OWN>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh) != hipSuccess) {
     set_error("peneo_pair_bwd_fused: cannot raise dynamic LDS to %zu bytes", sh);
     return PENEO_ERR_LAUNCH;
   }
-  hipLaunchKernelGGL((pair_bwd_one_kernel<KS, DROP>), dim3((unsigned)p.ntiles, (unsigned)p.B), dim3(PB_WAVES * 64), sh, st, p);
+  hipLaunchKernelGGL((pair_bwd_one_kernel<KS, DROP, OWN>), dim3((unsigned)p.ntiles, (unsigned)p.B), dim3(PB_WAVES * 64), sh, st, p);
   return check_launch("peneo_pair_bwd_fused");
 }
 
@@ -1571,7 +1582,8 @@ static int launch_pair_bwd(const PairBwdParams& p, hipStream_t st) {
 }
 template <int KS>
 static int launch_pair_bwd_1w(const PairBwdParams& p, hipStream_t st) {
-  return p.drop_thr16 ? launch_pair_bwd_one<KS, true>(p, st) : launch_pair_bwd_one<KS, false>(p, st);
+  if (p.ws_own) return p.drop_thr16 ? launch_pair_bwd_one<KS, true, true>(p, st) : launch_pair_bwd_one<KS, false, true>(p, st);
+  return p.drop_thr16 ? launch_pair_bwd_one<KS, true, false>(p, st) : launch_pair_bwd_one<KS, false, false>(p, st);
 }
 
 }  // namespace peneo
@@ -1617,6 +1629,12 @@ extern "C" size_t peneo_pair_bwd_partial_bytes(int B, int N, int D) {
   return (size_t)B * pb_num_tiles(N) * (PB_TI + PB_TJ) * D * sizeof(float);
 }
 
+// rows of the [rows][4 * nh*D] fp32 workspace of peneo_pair_bwd_fused / peneo_pair_bwd_saved under the mode in force
+extern "C" int64_t peneo_pair_bwd_workspace_rows(int B, int N) {
+  if (B <= 0 || N <= 0) return 0;
+  return det_mode() >= 1 ? (int64_t)B * pb_num_tiles(N) : (int64_t)PB_SLOTS;
+}
+
 extern "C" int peneo_pair_bwd_saved(int dtype, const void* ab, int B, int N, int D, const void* w_packed,
                                     const peneo_pair_dz_args* args, const void* act, void* dz, float* d_ab, float* workspace,
                                     float* partials, peneo_stream_t stream) {
@@ -1636,6 +1654,8 @@ extern "C" int peneo_pair_bwd_saved(int dtype, const void* ab, int B, int N, int
   p.drop_thr16 = pair_drop_thr16_host(args->drop_p); p.drop_seed = args->drop_seed; p.drop_scale = pair_drop_scale_host(args->drop_p);
   p.dbg = nullptr;
   p.part_a = partials; p.part_b = partials + (size_t)B * p.ntiles * PB_TI * D;
+  p.ws_own = det_mode() >= 1;
+  if (!p.ws_own) PENEO_ORDER_DEPENDENT("peneo_pair_bwd_saved");
   hipStream_t st = (hipStream_t)stream;
   const int rc = p.drop_thr16 ? launch_pair_bwd_sv<24, true>(p, st) : launch_pair_bwd_sv<24, false>(p, st);
   if (rc != PENEO_OK) return rc;
@@ -1665,6 +1685,8 @@ extern "C" int peneo_pair_bwd_fused(int dtype, const void* ab, int B, int N, int
   p.drop_thr16 = pair_drop_thr16_host(args->drop_p); p.drop_seed = args->drop_seed; p.drop_scale = pair_drop_scale_host(args->drop_p);
   p.dbg = g_pb_dbg;
   p.part_a = partials; p.part_b = partials + (size_t)B * p.ntiles * PB_TI * D;
+  p.ws_own = det_mode() >= 1;
+  if (!p.ws_own) PENEO_ORDER_DEPENDENT("peneo_pair_bwd_fused");
   hipStream_t st = (hipStream_t)stream;
   int rc = PENEO_ERR_INVALID;
   switch (D / 16) {

@@ -489,7 +489,9 @@ __global__ __launch_bounds__(256) void pair_x_fwd_rows_kernel(const T* abd, int 
 // dx rows; a 64-thread block owns (row i, one of JSPLIT slices of j), each thread 8 (bf16) / 4 (fp32) columns with
 // 16-byte loads, 4 rows in flight; the JSPLIT partial sums meet in fp32 atomics (JSPLIT * D per row: negligible).
 constexpr int JSPLIT = 4;
-template <typename T, bool PRE>   // PRE: dx already carries the SiLU'(a_i + b_j) factor (applied by the dx GEMM epilogue)
+// SPLIT = 1 (deterministic mode): one workgroup per row / column, so every address of d_ab receives one add per launch, and the
+// launches of a backward follow each other on one stream
+template <typename T, bool PRE, int SPLIT = JSPLIT>   // PRE: dx already carries the SiLU'(a_i + b_j) factor (applied by the dx GEMM epilogue)
 __global__ __launch_bounds__(256) void pair_x_bwd_a_kernel(const T* abd, int N, int D, int i0, int64_t pbase, const T* dx,
                                                           float* d_ab) {
   constexpr int VEC = Elem<T>::kVec;
@@ -497,7 +499,7 @@ __global__ __launch_bounds__(256) void pair_x_bwd_a_kernel(const T* abd, int N, 
   const int c = threadIdx.x * VEC;
   if (c >= D) return;
   const int len = N - i;
-  const int per = (len + JSPLIT - 1) / JSPLIT;
+  const int per = (len + SPLIT - 1) / SPLIT;
   const int j0 = i + blockIdx.y * per, j1 = min(N, j0 + per);
   if (j0 >= j1) return;
   const int64_t prow = pair_row_start(i, N) - pbase;
@@ -533,7 +535,7 @@ __global__ __launch_bounds__(256) void pair_x_bwd_a_kernel(const T* abd, int N, 
   for (int e = 0; e < VEC; ++e) atomicAdd(d_ab + (int64_t)i * 2 * D + c + e, s[e]);
 }
 // d_b[j, k] += sum_{i0 <= i < i1, i <= j} dx[p(i,j), k] * SiLU'(a_i[k] + b_j[k]): block = (column j, slice of i)
-template <typename T, bool PRE>
+template <typename T, bool PRE, int SPLIT = JSPLIT>
 __global__ __launch_bounds__(256) void pair_x_bwd_b_kernel(const T* abd, int N, int D, int i0, int i1, int64_t pbase, const T* dx,
                                                           float* d_ab) {
   constexpr int VEC = Elem<T>::kVec;
@@ -541,7 +543,7 @@ __global__ __launch_bounds__(256) void pair_x_bwd_b_kernel(const T* abd, int N, 
   const int c = threadIdx.x * VEC;
   if (c >= D) return;
   const int iend = min(i1, j + 1);
-  const int per = (iend - i0 + JSPLIT - 1) / JSPLIT;
+  const int per = (iend - i0 + SPLIT - 1) / SPLIT;
   const int ia = i0 + blockIdx.y * per, ib = min(iend, ia + per);
   if (ia >= ib) return;
   float bj[VEC], s[VEC];
@@ -1208,6 +1210,7 @@ struct DzFusedParams {
   peneo_pair_dz_args a;
   bf16_t* out; float* ws;
   bf16_t* x_out; bf16_t* pre_out;   // optional [npairs, D]: SiLU(a_i + b_j) and a_i + b_j for the dW1 / dx GEMMs
+  int ws_own;                       // deterministic mode: workspace row = workgroup (one add per address and launch), else % DZF_SLOTS
 };
 constexpr int DZF_SLOTS = 256;
 
@@ -1311,7 +1314,7 @@ __global__ __launch_bounds__(PH_WAVES * 64, 2) void pair_dz_fused_kernel(DzFused
   for (int s0 = 0; s0 < NSTAGE - 1; ++s0)
     if (s0 < nslab) dma(s0, s0);
 
-  float* slot = p.ws + (int64_t)(blockIdx.x % DZF_SLOTS) * 4 * ncol;
+  float* slot = p.ws + (int64_t)(p.ws_own ? blockIdx.x : blockIdx.x % DZF_SLOTS) * 4 * ncol;
   // the wave that owns slab s adds the eight waves' column sums of that slab to the workspace
   auto flush = [&](int s) {
     if (wave == (s & (PH_WAVES - 1)) && lane < 32) {
@@ -1636,15 +1639,22 @@ extern "C" int peneo_pair_x_bwd(int dtype, const void* ab_doc, int N, int D, int
                 "peneo_pair_x_bwd: pointers must be 16-byte aligned");
   const int64_t pbase = pair_row_start(i0, N);
   hipStream_t st = (hipStream_t)stream;
-#define PENEO_XBWD(T_, PRE_)                                                                                                   \
+  const bool det = det_mode() >= 1;
+  if (!det) PENEO_ORDER_DEPENDENT("peneo_pair_x_bwd");   // the JSPLIT workgroups of a row add into d_ab with fp32 atomics
+#define PENEO_XBWD(T_, PRE_, SPLIT_)                                                                                           \
   {                                                                                                                           \
-    hipLaunchKernelGGL((pair_x_bwd_a_kernel<T_, PRE_>), dim3(i1 - i0, JSPLIT), dim3(threads), 0, st, (const T_*)ab_doc, N, D, i0, \
+    hipLaunchKernelGGL((pair_x_bwd_a_kernel<T_, PRE_, SPLIT_>), dim3(i1 - i0, SPLIT_), dim3(threads), 0, st, (const T_*)ab_doc, N, D, i0, \
                        pbase, (const T_*)dx, d_ab_doc);                                                                       \
-    hipLaunchKernelGGL((pair_x_bwd_b_kernel<T_, PRE_>), dim3(N - i0, JSPLIT), dim3(threads), 0, st, (const T_*)ab_doc, N, D, i0, \
+    hipLaunchKernelGGL((pair_x_bwd_b_kernel<T_, PRE_, SPLIT_>), dim3(N - i0, SPLIT_), dim3(threads), 0, st, (const T_*)ab_doc, N, D, i0, \
                        i1, pbase, (const T_*)dx, d_ab_doc);                                                                   \
   }
-  if (dtype == PENEO_BF16) { if (premultiplied) PENEO_XBWD(bf16_t, true) else PENEO_XBWD(bf16_t, false) }
-  else { if (premultiplied) PENEO_XBWD(float, true) else PENEO_XBWD(float, false) }
+#define PENEO_XBWD_T(T_)                                                                       \
+  {                                                                                            \
+    if (det) { if (premultiplied) PENEO_XBWD(T_, true, 1) else PENEO_XBWD(T_, false, 1) }      \
+    else { if (premultiplied) PENEO_XBWD(T_, true, JSPLIT) else PENEO_XBWD(T_, false, JSPLIT) } \
+  }
+  if (dtype == PENEO_BF16) PENEO_XBWD_T(bf16_t) else PENEO_XBWD_T(float)
+#undef PENEO_XBWD_T
 #undef PENEO_XBWD
   return check_launch("peneo_pair_x_bwd");
 }
@@ -1666,6 +1676,10 @@ extern "C" int peneo_pair_dz_fused(int dtype, const void* ab_doc, int N, int D, 
   PENEO_REQUIRE((reinterpret_cast<uintptr_t>(ab_doc) & 15) == 0, "peneo_pair_dz_fused: ab must be 16-byte aligned");
   PENEO_REQUIRE(args->drop_p >= 0.f && args->drop_p < 1.f, "peneo_pair_dz_fused: drop_p must be in [0, 1)");
   DzFusedParams p;
+  // deterministic mode: a workspace row per workgroup of the launch (peneo_pair_dz_fused_workspace_rows), so every address receives
+  // one add per launch, and the launches of a backward follow each other on one stream
+  p.ws_own = det_mode() >= 1;
+  if (!p.ws_own) PENEO_ORDER_DEPENDENT("peneo_pair_dz_fused");   // workgroups share the workspace rows (fp32 atomics)
   p.abd = reinterpret_cast<const bf16_t*>(ab_doc); p.N = N; p.D = D;
   p.pbase = pair_row_start(i0, N); p.npairs = pair_row_start(i1, N) - p.pbase;
   p.wp = w_packed; p.b1 = b1; p.a = *args; p.out = reinterpret_cast<bf16_t*>(dz); p.ws = workspace;
@@ -1682,6 +1696,13 @@ extern "C" int peneo_pair_dz_fused(int dtype, const void* ab_doc, int N, int D, 
     case 32: return launch_pair_dz_fused<32>(p, st);
     default: set_error("peneo_pair_dz_fused: D=%d not supported (D/16 in {2,4,6,8,12,16,24,32})", D); return PENEO_ERR_INVALID;
   }
+}
+
+// rows of peneo_pair_dz_fused's [rows][4 * nh*D] workspace for launches of up to `npairs` pairs, under the mode in force
+extern "C" int64_t peneo_pair_dz_fused_workspace_rows(int64_t npairs) {
+  if (npairs <= 0) return 0;
+  const int64_t blocks = (npairs + PH_PAIRS - 1) / PH_PAIRS;
+  return det_mode() >= 1 && blocks > DZF_SLOTS ? blocks : (int64_t)DZF_SLOTS;
 }
 
 extern "C" size_t peneo_pair_dz_workspace_bytes(int num_heads, int D) { return (size_t)DZ_SLOTS * 4 * num_heads * D * sizeof(float); }
@@ -1722,6 +1743,7 @@ extern "C" int peneo_loss_finish(const float* partials, int64_t n_partials, cons
 extern "C" int peneo_weighted_ce(const float* logits, const int64_t* tags, const float* class_weight, int64_t rows, int C,
                                  float* num, float* den, float* dlogits, peneo_stream_t stream) {
   PENEO_REQUIRE(logits && tags && num && den && rows > 0 && C > 0 && C <= 16, "peneo_weighted_ce: bad arguments");
+  PENEO_ORDER_DEPENDENT("peneo_weighted_ce");   // every wave adds its numerator / denominator into the two result words
   hipLaunchKernelGGL(weighted_ce_kernel, dim3(cap_blocks(rows, 256, 1024)), dim3(256), 0, (hipStream_t)stream, logits, tags,
                      class_weight, rows, C, num, den, dlogits);
   return check_launch("peneo_weighted_ce");

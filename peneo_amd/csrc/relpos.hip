@@ -63,6 +63,29 @@ constexpr int RB_REP = 32;
 // lane-ops/s, the integer one (ds_add_u64) at ~4.6 T (tools/ubench/lds_atomic.hip), and integer sums are order-independent.
 __device__ __forceinline__ unsigned long long rb_fix(float v) { return (unsigned long long)__float2ll_rn(v * 4294967296.0f); }
 __device__ __forceinline__ float rb_unfix(unsigned long long q) { return (float)((double)(long long)q * (1.0 / 4294967296.0)); }
+// Deterministic form of the fold (peneo_set_deterministic; DET instantiations of the two kernels below): a workgroup adds its
+// per-bin sums to a 64-bit fixed-point accumulator per (head, bin) in the caller's workspace - integer adds, the same 2^-32 units -
+// and relpos_fold_finish_kernel converts every bin once.  Representable range: |sum over the launch of a bin| < 2^31 (about 2.1e9) at
+// a resolution of 2^-32 (2.3e-10); an addend is rounded to that grid before it is added, so n addends are off by at most n 2^-33.
+// The DET kernels take the three accumulator tables through the dw1 / dwx / dwy parameters.
+__device__ __forceinline__ void rb_fold_fixed(float* q1, float* qx, float* qy, int h, int i, int bins1, int bins2, unsigned long long acc) {
+  unsigned long long* d = nullptr;
+  if (i < bins1) { if (q1) d = reinterpret_cast<unsigned long long*>(q1) + h * bins1 + i; }
+  else if (i < bins1 + bins2) { if (qx) d = reinterpret_cast<unsigned long long*>(qx) + h * bins2 + (i - bins1); }
+  else if (qy) d = reinterpret_cast<unsigned long long*>(qy) + h * bins2 + (i - bins1 - bins2);
+  if (d) atomicAdd(d, acc);
+}
+__global__ __launch_bounds__(256) void relpos_fold_finish_kernel(const unsigned long long* acc, int n1, int n2, float scale, float* dw1,
+                                                                 float* dwx, float* dwy) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n1 + 2 * n2) return;
+  const float sum = rb_unfix(acc[i]) * scale;
+  if (i < n1) { if (dw1) dw1[i] += sum; }
+  else if (i < n1 + n2) { if (dwx) dwx[i - n1] += sum; }
+  else if (dwy) dwy[i - n1 - n2] += sum;
+}
+
+template <bool DET>
 __global__ __launch_bounds__(256) void relpos_bias_bwd_kernel(const float* g, const uint8_t* bk1, const uint8_t* bkx,
                                                               const uint8_t* bky, float* dw1, int bins1, float* dwx, float* dwy,
                                                               int bins2, float scale, int nh, int Tn, int64_t ldg) {
@@ -105,16 +128,21 @@ __global__ __launch_bounds__(256) void relpos_bias_bwd_kernel(const float* g, co
     unsigned long long acc = 0ull;
 #pragma unroll 8
     for (int r = 0; r < RB_REP; ++r) acc += hist[i * RB_REP + ((r + i) & (RB_REP - 1))];
-    const float sum = rb_unfix(acc) * scale;
-    if (i < bins1) { if (dw1) atomicAdd(dw1 + h * bins1 + i, sum); }
-    else if (i < bins1 + bins2) { if (dwx) atomicAdd(dwx + h * bins2 + (i - bins1), sum); }
-    else if (dwy) atomicAdd(dwy + h * bins2 + (i - bins1 - bins2), sum);
+    if constexpr (DET) {
+      rb_fold_fixed(dw1, dwx, dwy, h, i, bins1, bins2, acc);
+    } else {
+      const float sum = rb_unfix(acc) * scale;
+      if (i < bins1) { if (dw1) atomicAdd(dw1 + h * bins1 + i, sum); }
+      else if (i < bins1 + bins2) { if (dwx) atomicAdd(dwx + h * bins2 + (i - bins1), sum); }
+      else if (dwy) atomicAdd(dwy + h * bins2 + (i - bins1 - bins2), sum);
+    }
   }
 }
 
 // same reduction from L per-layer bf16 dS^T buffers [B, nh, T keys, Tp queries]: block = (b, h, 32-key slab).
 // Work item = 8 consecutive queries of one key row: L 16-byte loads (one per layer) summed in fp32, three 8-byte bucket
 // loads (the transposed maps are padded to row stride Tp, so both are aligned), then the LDS integer atomics.
+template <bool DET>
 __global__ __launch_bounds__(256) void relpos_bias_bwd_layers_kernel(const bf16_t* ds, int L, int64_t lstride, const uint8_t* bk1,
                                                                      const uint8_t* bkx, const uint8_t* bky, float* dw1, int bins1,
                                                                      float* dwx, float* dwy, int bins2, float scale, int nh, int Tn,
@@ -182,34 +210,88 @@ __global__ __launch_bounds__(256) void relpos_bias_bwd_layers_kernel(const bf16_
     unsigned long long acc = 0ull;
 #pragma unroll 8
     for (int r = 0; r < RB_REP; ++r) acc += hist[i * RB_REP + ((r + i) & (RB_REP - 1))];
-    const float sum = rb_unfix(acc) * scale;
-    if (i < bins1) { if (dw1) atomicAdd(dw1 + h * bins1 + i, sum); }
-    else if (i < bins1 + bins2) { if (dwx) atomicAdd(dwx + h * bins2 + (i - bins1), sum); }
-    else if (dwy) atomicAdd(dwy + h * bins2 + (i - bins1 - bins2), sum);
+    if constexpr (DET) {
+      rb_fold_fixed(dw1, dwx, dwy, h, i, bins1, bins2, acc);
+    } else {
+      const float sum = rb_unfix(acc) * scale;
+      if (i < bins1) { if (dw1) atomicAdd(dw1 + h * bins1 + i, sum); }
+      else if (i < bins1 + bins2) { if (dwx) atomicAdd(dwx + h * bins2 + (i - bins1), sum); }
+      else if (dwy) atomicAdd(dwy + h * bins2 + (i - bins1 - bins2), sum);
+    }
   }
 }
 
 }  // namespace peneo
 using namespace peneo;
 
+// The fixed-point accumulators of the deterministic fold: [nh * bins1 | nh * bins2 | nh * bins2] 64-bit words
+extern "C" size_t peneo_relpos_bwd_workspace_bytes(int nh, int bins1, int bins2) {
+  if (det_mode() == 0 || nh <= 0 || bins1 < 0 || bins2 < 0) return 0;
+  return sizeof(unsigned long long) * (size_t)nh * (size_t)(bins1 + 2 * bins2);
+}
+// the accumulator tables of a deterministic launch (cleared here; a table nobody asked for stays NULL), as the kernels' dw1 / dwx / dwy
+struct RelposFixed { float* q1; float* qx; float* qy; };
+static int relpos_fixed_begin(const char* who, void* ws, size_t ws_bytes, int nh, int bins1, int bins2, float* dw1, float* dwx, float* dwy,
+                              hipStream_t st, RelposFixed* out) {
+  const size_t need = peneo_relpos_bwd_workspace_bytes(nh, bins1, bins2);
+  PENEO_REQUIRE(ws && (reinterpret_cast<uintptr_t>(ws) & 7) == 0 && ws_bytes >= need,
+                "%s: workspace of %zu bytes, 8-byte aligned, needed under the deterministic mode (got %zu)", who, need, ws_bytes);
+  if (hipMemsetAsync(ws, 0, need, st) != hipSuccess) { set_error("%s: memset failed", who); return PENEO_ERR_LAUNCH; }
+  unsigned long long* q = reinterpret_cast<unsigned long long*>(ws);
+  out->q1 = dw1 ? reinterpret_cast<float*>(q) : nullptr;
+  out->qx = dwx ? reinterpret_cast<float*>(q + (size_t)nh * bins1) : nullptr;
+  out->qy = dwy ? reinterpret_cast<float*>(q + (size_t)nh * (bins1 + bins2)) : nullptr;
+  return PENEO_OK;
+}
+static int relpos_fixed_end(const char* who, void* ws, int nh, int bins1, int bins2, float scale, float* dw1, float* dwx, float* dwy, hipStream_t st) {
+  const int n = nh * (bins1 + 2 * bins2);
+  hipLaunchKernelGGL(relpos_fold_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, reinterpret_cast<const unsigned long long*>(ws),
+                     nh * bins1, nh * bins2, scale, dw1, dwx, dwy);
+  return check_launch(who);
+}
+
+static int relpos_bwd_layers_impl(const char* who, const void* ds, int L, int64_t layer_stride, const uint8_t* bk1_t, const uint8_t* bkx_t,
+                                  const uint8_t* bky_t, float* dw1, int bins1, float* dwx, float* dwy, int bins2, float scale, int B, int nh,
+                                  int T, int Tp, bool det, void* ws, size_t ws_bytes, peneo_stream_t stream) {
+  PENEO_REQUIRE(ds && L > 0 && B > 0 && nh > 0 && T > 0 && Tp >= T, "%s: bad arguments", who);
+  PENEO_REQUIRE((bkx_t != nullptr) == (bky_t != nullptr), "%s: 2-D inputs mismatch", who);
+  PENEO_REQUIRE(L == 1 || layer_stride >= (int64_t)B * nh * T * Tp, "%s: layer stride too small", who);
+  PENEO_REQUIRE(Tp % 8 == 0 && (reinterpret_cast<uintptr_t>(ds) & 15) == 0 && (layer_stride % 8) == 0,
+                "%s: dS^T rows must be 16-byte aligned (Tp multiple of 8)", who);
+  PENEO_REQUIRE(((reinterpret_cast<uintptr_t>(bk1_t) | reinterpret_cast<uintptr_t>(bkx_t) | reinterpret_cast<uintptr_t>(bky_t)) & 7) == 0,
+                "%s: bucket maps must be 8-byte aligned", who);
+  size_t sh = sizeof(unsigned long long) * (size_t)(bins1 + 2 * bins2) * RB_REP;
+  PENEO_REQUIRE(sh <= 64 * 1024, "%s: tables too large for LDS", who);
+  int slabs = (T + 31) / 32;
+  dim3 grid((unsigned)((int64_t)B * nh * slabs));
+  hipStream_t st = (hipStream_t)stream;
+  if (det) {
+    RelposFixed q;
+    const int rc = relpos_fixed_begin(who, ws, ws_bytes, nh, bins1, bins2, dw1, dwx, dwy, st, &q);
+    if (rc) return rc;
+    hipLaunchKernelGGL(relpos_bias_bwd_layers_kernel<true>, grid, dim3(256), sh, st, (const bf16_t*)ds, L, layer_stride, bk1_t, bkx_t, bky_t,
+                       q.q1, bins1, q.qx, q.qy, bins2, scale, nh, T, Tp);
+    return relpos_fixed_end(who, ws, nh, bins1, bins2, scale, dw1, dwx, dwy, st);
+  }
+  PENEO_ORDER_DEPENDENT(who);
+  hipLaunchKernelGGL(relpos_bias_bwd_layers_kernel<false>, grid, dim3(256), sh, st, (const bf16_t*)ds, L, layer_stride,
+                     bk1_t, bkx_t, bky_t, dw1, bins1, dwx, dwy, bins2, scale, nh, T, Tp);
+  return check_launch(who);
+}
+
 extern "C" int peneo_relpos_bias_bwd_layers(const void* ds, int L, int64_t layer_stride, const uint8_t* bk1_t,
                                             const uint8_t* bkx_t, const uint8_t* bky_t, float* dw1, int bins1, float* dwx,
                                             float* dwy, int bins2, float scale, int B, int nh, int T, int Tp,
                                             peneo_stream_t stream) {
-  PENEO_REQUIRE(ds && L > 0 && B > 0 && nh > 0 && T > 0 && Tp >= T, "peneo_relpos_bias_bwd_layers: bad arguments");
-  PENEO_REQUIRE((bkx_t != nullptr) == (bky_t != nullptr), "peneo_relpos_bias_bwd_layers: 2-D inputs mismatch");
-  PENEO_REQUIRE(L == 1 || layer_stride >= (int64_t)B * nh * T * Tp, "peneo_relpos_bias_bwd_layers: layer stride too small");
-  PENEO_REQUIRE(Tp % 8 == 0 && (reinterpret_cast<uintptr_t>(ds) & 15) == 0 && (layer_stride % 8) == 0,
-                "peneo_relpos_bias_bwd_layers: dS^T rows must be 16-byte aligned (Tp multiple of 8)");
-  PENEO_REQUIRE(((reinterpret_cast<uintptr_t>(bk1_t) | reinterpret_cast<uintptr_t>(bkx_t) | reinterpret_cast<uintptr_t>(bky_t)) & 7) == 0,
-                "peneo_relpos_bias_bwd_layers: bucket maps must be 8-byte aligned");
-  size_t sh = sizeof(unsigned long long) * (size_t)(bins1 + 2 * bins2) * RB_REP;
-  PENEO_REQUIRE(sh <= 64 * 1024, "peneo_relpos_bias_bwd_layers: tables too large for LDS");
-  int slabs = (T + 31) / 32;
-  dim3 grid((unsigned)((int64_t)B * nh * slabs));
-  hipLaunchKernelGGL(relpos_bias_bwd_layers_kernel, grid, dim3(256), sh, (hipStream_t)stream, (const bf16_t*)ds, L, layer_stride,
-                     bk1_t, bkx_t, bky_t, dw1, bins1, dwx, dwy, bins2, scale, nh, T, Tp);
-  return check_launch("peneo_relpos_bias_bwd_layers");
+  return relpos_bwd_layers_impl("peneo_relpos_bias_bwd_layers", ds, L, layer_stride, bk1_t, bkx_t, bky_t, dw1, bins1, dwx, dwy, bins2, scale,
+                                B, nh, T, Tp, false, nullptr, 0, stream);
+}
+extern "C" int peneo_relpos_bias_bwd_layers_ws(const void* ds, int L, int64_t layer_stride, const uint8_t* bk1_t,
+                                               const uint8_t* bkx_t, const uint8_t* bky_t, float* dw1, int bins1, float* dwx,
+                                               float* dwy, int bins2, float scale, int B, int nh, int T, int Tp, void* workspace,
+                                               size_t workspace_bytes, peneo_stream_t stream) {
+  return relpos_bwd_layers_impl("peneo_relpos_bias_bwd_layers_ws", ds, L, layer_stride, bk1_t, bkx_t, bky_t, dw1, bins1, dwx, dwy, bins2,
+                                scale, B, nh, T, Tp, det_mode() >= 1, workspace, workspace_bytes, stream);
 }
 
 // Inputs of the bucket kernel and the key mask over text + visual tokens in one launch (they used to be a dozen torch
@@ -272,17 +354,38 @@ extern "C" int peneo_relpos_bias_fwd(int dtype, const uint8_t* bk1, const uint8_
   return check_launch("peneo_relpos_bias_fwd");
 }
 
+static int relpos_bwd_impl(const char* who, const float* g, int64_t ldg, const uint8_t* bk1, const uint8_t* bkx, const uint8_t* bky, float* dw1,
+                           int bins1, float* dwx, float* dwy, int bins2, float scale, int B, int nh, int T, bool det, void* ws,
+                           size_t ws_bytes, peneo_stream_t stream) {
+  PENEO_REQUIRE(ldg >= T, "%s: ldg < T", who);
+  PENEO_REQUIRE(g && B > 0 && nh > 0 && T > 0, "%s: bad arguments", who);
+  PENEO_REQUIRE((bkx != nullptr) == (bky != nullptr), "%s: 2-D inputs mismatch", who);
+  size_t sh = sizeof(unsigned long long) * (size_t)(bins1 + 2 * bins2) * RB_REP;
+  PENEO_REQUIRE(sh <= 64 * 1024, "%s: tables too large for LDS", who);
+  int slabs = (T + 31) / 32;
+  dim3 grid((unsigned)((int64_t)B * nh * slabs));
+  hipStream_t st = (hipStream_t)stream;
+  if (det) {
+    RelposFixed q;
+    const int rc = relpos_fixed_begin(who, ws, ws_bytes, nh, bins1, bins2, dw1, dwx, dwy, st, &q);
+    if (rc) return rc;
+    hipLaunchKernelGGL(relpos_bias_bwd_kernel<true>, grid, dim3(256), sh, st, g, bk1, bkx, bky, q.q1, bins1, q.qx, q.qy, bins2, scale, nh, T, ldg);
+    return relpos_fixed_end(who, ws, nh, bins1, bins2, scale, dw1, dwx, dwy, st);
+  }
+  PENEO_ORDER_DEPENDENT(who);
+  hipLaunchKernelGGL(relpos_bias_bwd_kernel<false>, grid, dim3(256), sh, st, g, bk1, bkx, bky, dw1, bins1, dwx, dwy,
+                     bins2, scale, nh, T, ldg);
+  return check_launch(who);
+}
+
 extern "C" int peneo_relpos_bias_bwd(const float* g, int64_t ldg, const uint8_t* bk1, const uint8_t* bkx, const uint8_t* bky,
                                      float* dw1, int bins1, float* dwx, float* dwy, int bins2, float scale, int B, int nh, int T,
                                      peneo_stream_t stream) {
-  PENEO_REQUIRE(ldg >= T, "peneo_relpos_bias_bwd: ldg < T");
-  PENEO_REQUIRE(g && B > 0 && nh > 0 && T > 0, "peneo_relpos_bias_bwd: bad arguments");
-  PENEO_REQUIRE((bkx != nullptr) == (bky != nullptr), "peneo_relpos_bias_bwd: 2-D inputs mismatch");
-  size_t sh = sizeof(unsigned long long) * (size_t)(bins1 + 2 * bins2) * RB_REP;
-  PENEO_REQUIRE(sh <= 64 * 1024, "peneo_relpos_bias_bwd: tables too large for LDS");
-  int slabs = (T + 31) / 32;
-  dim3 grid((unsigned)((int64_t)B * nh * slabs));
-  hipLaunchKernelGGL(relpos_bias_bwd_kernel, grid, dim3(256), sh, (hipStream_t)stream, g, bk1, bkx, bky, dw1, bins1, dwx, dwy,
-                     bins2, scale, nh, T, ldg);
-  return check_launch("peneo_relpos_bias_bwd");
+  return relpos_bwd_impl("peneo_relpos_bias_bwd", g, ldg, bk1, bkx, bky, dw1, bins1, dwx, dwy, bins2, scale, B, nh, T, false, nullptr, 0, stream);
+}
+extern "C" int peneo_relpos_bias_bwd_ws(const float* g, int64_t ldg, const uint8_t* bk1, const uint8_t* bkx, const uint8_t* bky,
+                                        float* dw1, int bins1, float* dwx, float* dwy, int bins2, float scale, int B, int nh, int T,
+                                        void* workspace, size_t workspace_bytes, peneo_stream_t stream) {
+  return relpos_bwd_impl("peneo_relpos_bias_bwd_ws", g, ldg, bk1, bkx, bky, dw1, bins1, dwx, dwy, bins2, scale, B, nh, T, det_mode() >= 1,
+                         workspace, workspace_bytes, stream);
 }

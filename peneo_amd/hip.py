@@ -215,6 +215,16 @@ SIGNATURES = {
     "peneo_gemm_set_sk_mode": (None, [_i]),
     "peneo_gemm_sk_set_prof": (None, [_vp]),
     "peneo_gemm_sk_set_max_groups": (None, [_i]),
+    "peneo_set_deterministic": (None, [_i]),    # deterministic mode: process-wide like the switches above
+    "peneo_deterministic": (_i, []),
+    "peneo_order_dependent_launches": (C.c_uint64, []),
+    "peneo_pair_bwd_workspace_rows": (_i64, [_i, _i]),
+    "peneo_pair_dz_fused_workspace_rows": (_i64, [_i64]),
+    "peneo_relpos_bwd_workspace_bytes": (_sz, [_i, _i, _i]),
+    "peneo_relpos_bias_bwd_layers_ws": (_i, [_vp, _i, _i64, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _f, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "peneo_relpos_bias_bwd_ws": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _f, _i, _i, _i, _vp, _sz, _vp]),
+    "peneo_grad_sqnorm_workspace_bytes": (_sz, [_i]),
+    "peneo_grad_sqnorm_ws": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None
@@ -246,6 +256,48 @@ def check(rc: int, what: str = "") -> None:
     if rc != 0:
         msg = lib().peneo_last_error().decode("utf-8", "replace")
         raise PeneoHipError(f"{what or 'peneo_hip'} failed ({rc}): {msg}")
+
+
+# ----------------------------------------------------------------------------------------------
+# deterministic mode (include/peneo_hip.h: peneo_set_deterministic)
+# ----------------------------------------------------------------------------------------------
+def set_deterministic(flag_or_mode) -> None:
+    """False / 0: off.  True / 1: every launcher that has an order-independent form uses it.  2: strict - a call that would still
+    take an order-dependent accumulation path raises.  Process-wide; set it while no kernel call is being issued on another thread."""
+    mode = int(flag_or_mode)
+    if mode not in (0, 1, 2):
+        raise ValueError(f"deterministic mode must be 0, 1 or 2 (got {flag_or_mode!r})")
+    lib().peneo_set_deterministic(mode)
+
+
+def deterministic_mode() -> int:
+    return int(lib().peneo_deterministic())
+
+
+def is_deterministic() -> bool:
+    return deterministic_mode() != 0
+
+
+def order_dependent_launches() -> int:
+    """Calls of this process that took an order-dependent accumulation path (any mode)."""
+    return int(lib().peneo_order_dependent_launches())
+
+
+class deterministic:
+    """``with peneo_amd.deterministic(): ...`` - the mode (default 2, strict) inside, what was in force before restored after."""
+
+    def __init__(self, mode=2):
+        self.mode = int(mode)
+        self._prev = None
+
+    def __enter__(self):
+        self._prev = deterministic_mode()
+        set_deterministic(self.mode)
+        return self
+
+    def __exit__(self, *exc):
+        set_deterministic(self._prev)
+        return False
 
 
 # ----------------------------------------------------------------------------------------------

@@ -20,7 +20,7 @@ import torch.nn as nn
 from transformers.modeling_outputs import ModelOutput
 
 from .. import ops
-from ..hip import ACT_NONE, ACT_SILU, PeneoHipError
+from ..hip import ACT_NONE, ACT_SILU, PeneoHipError, deterministic_mode
 from .engine import DropoutSeeds, WeightCache, big_acquire, big_clear, big_release, can_defer, defer_join, join_pending, mark_late
 
 HEAD_NAMES = ("line_extraction", "ent_linking_h2h", "ent_linking_t2t", "line_grouping_h2h", "line_grouping_t2t")
@@ -210,6 +210,20 @@ class _DecoderStage(torch.autograd.Function):
         kcls = dec.num_cls_layers
         heads = [tuple(next(it) for _ in range(2 * kcls)) for _ in HEAD_NAMES]
         D = wc_w.shape[0]
+        if need_grad and tags is not None and deterministic_mode() == 2:
+            # strict deterministic mode: say which piece of this step has no order-independent backward, before any of it runs
+            nh_ = len(HEAD_NAMES)
+            what = ("fp32 compute (the chunked decoder backward adds into d_ab and the pair_dz workspace with float atomics)"
+                    if dt != torch.bfloat16 else
+                    f"a {kcls}-layer classifier (only the 2-layer heads have the fused backward; peneo_weighted_ce uses float atomics)"
+                    if kcls != 2 else
+                    "OHEM (peneo_ohem_ce sums the kept pairs with float atomics)" if dec.le_loss.ohem else
+                    f"the decoder backward at D = {D} without peneo_pair_bwd_fused and peneo_pair_dz_fused (the pair_dz GEMM epilogue "
+                    "adds with float atomics)"
+                    if not ((dec.fused_bwd and ops.pair_bwd_supported(dt, D, nh_)) or
+                            (dec.fused_dz and D % 32 == 0 and D // 16 in (2, 4, 6, 8, 12, 16, 24, 32))) else None)
+            if what:
+                raise ValueError(f"deterministic mode 2 does not cover {what}; use mode 1 to run it and count it")
         seeds = DropoutSeeds(dec.training, dec.dropout_p, 0.0)
         dev = seq.device
         saved = dict(seeds=seeds)
@@ -368,7 +382,9 @@ class _DecoderStage(torch.autograd.Function):
         use_fused_bwd = dec.fused_bwd and ops.pair_bwd_supported(dt, D, nh)   # (LDS: the head count enters, D = 512 holds 5 heads)
         # rows the dz producers spread their partial sums over: 256 for the fused kernels / the GEMM epilogue, the full
         # 1024 for the stand-alone peneo_pair_dz (the chunked path with the classifier dropout active)
-        dz_ws = ops.pair_dz_workspace(nh, D, dev, slots=256 if (use_fused_bwd or drop_p == 0.0) else None)
+        # (the fused kernels under the deterministic mode: one row per workgroup of the launch, ops.pair_bwd_workspace asks the library)
+        dz_ws = ops.pair_bwd_workspace(B, N, nh, D, dev) if use_fused_bwd else \
+            ops.pair_dz_workspace(nh, D, dev, slots=256 if drop_p == 0.0 else None)
         # the fused kernel overwrites d_ab; the chunked path accumulates into it
         d_ab = (torch.empty if use_fused_bwd else torch.zeros)((B, N, 2 * D), dtype=torch.float32, device=dev)
         if use_fused_bwd:
@@ -445,6 +461,9 @@ class _DecoderStage(torch.autograd.Function):
         # peneo_pair_dz kernel: the GEMM's pair-dz epilogue does not regenerate the mask)
         fused_dz = (dec.fused_dz and dt == torch.bfloat16 and D % 32 == 0
                     and D // 16 in (2, 4, 6, 8, 12, 16, 24, 32))
+        if fused_dz and dz_ws.shape[0] < ops.pair_dz_fused_workspace_rows(maxp):
+            # (deterministic mode: peneo_pair_dz_fused gives every workgroup of a launch a workspace row of its own)
+            dz_ws = torch.zeros((ops.pair_dz_fused_workspace_rows(maxp), 4 * nh * D), dtype=torch.float32, device=dev)
         if fused_dz:
             wp = wc.get(("dec.pack", dt), w1s + w2s, lambda: ops.pair_heads_pack(dt, [w.detach() for w in w1s],
                                                                                  [w.detach() for w in w2s]))

@@ -585,18 +585,26 @@ def relpos_bias_bwd_layers(ds: torch.Tensor, bk1_t, bkx_t, bky_t, dw1, dwx, dwy,
         out[:, :, :T] = t
         return out
     bk1_t, bkx_t, bky_t = padded(bk1_t), padded(bkx_t), padded(bky_t)
-    check(lib().peneo_relpos_bias_bwd_layers(ptr(_c(ds)), L, ds.stride(0), ptr(bk1_t), ptr(bkx_t), ptr(bky_t), ptr(dw1),
-                                             dw1.shape[1] if dw1 is not None else 0, ptr(dwx), ptr(dwy),
-                                             dwx.shape[1] if dwx is not None else 0, scale, B, nh, T, Tp, stream()),
-          "peneo_relpos_bias_bwd_layers")
+    bins1, bins2 = dw1.shape[1] if dw1 is not None else 0, dwx.shape[1] if dwx is not None else 0
+    ws, ws_bytes = _relpos_bwd_workspace(nh, bins1, bins2, ds.device)
+    check(lib().peneo_relpos_bias_bwd_layers_ws(ptr(_c(ds)), L, ds.stride(0), ptr(bk1_t), ptr(bkx_t), ptr(bky_t), ptr(dw1), bins1,
+                                                ptr(dwx), ptr(dwy), bins2, scale, B, nh, T, Tp, ptr(ws), ws_bytes, stream()),
+          "peneo_relpos_bias_bwd_layers_ws")
+
+
+def _relpos_bwd_workspace(nh: int, bins1: int, bins2: int, device):
+    """The fixed-point accumulators of the deterministic fold (None, 0 while the mode is off: the plain kernels)."""
+    need = int(lib().peneo_relpos_bwd_workspace_bytes(nh, bins1, bins2))
+    return (torch.empty((need + 7) // 8, dtype=torch.int64, device=device), need) if need else (None, 0)
 
 
 def relpos_bias_bwd(g: torch.Tensor, bk1, bkx, bky, dw1, dwx, dwy, scale: float) -> None:
     B, nh, T, ldg = g.shape
-    check(lib().peneo_relpos_bias_bwd(ptr(_c(g)), ldg, ptr(bk1), ptr(bkx), ptr(bky), ptr(dw1),
-                                      dw1.shape[1] if dw1 is not None else 0, ptr(dwx), ptr(dwy),
-                                      dwx.shape[1] if dwx is not None else 0, scale, B, nh, T, stream()),
-          "peneo_relpos_bias_bwd")
+    bins1, bins2 = dw1.shape[1] if dw1 is not None else 0, dwx.shape[1] if dwx is not None else 0
+    ws, ws_bytes = _relpos_bwd_workspace(nh, bins1, bins2, g.device)
+    check(lib().peneo_relpos_bias_bwd_ws(ptr(_c(g)), ldg, ptr(bk1), ptr(bkx), ptr(bky), ptr(dw1), bins1, ptr(dwx), ptr(dwy), bins2,
+                                         scale, B, nh, T, ptr(ws), ws_bytes, stream()),
+          "peneo_relpos_bias_bwd_ws")
 
 
 # ----------------------------------------------------------------------------------------------
@@ -1106,6 +1114,11 @@ def pair_dz_workspace(nh: int, D: int, device, slots: Optional[int] = None) -> t
     return torch.zeros((full if slots is None else min(slots, full), 4 * nh * D), dtype=torch.float32, device=device)
 
 
+def pair_dz_fused_workspace_rows(npairs: int) -> int:
+    """Rows of ``pair_dz_fused``'s workspace for launches of up to `npairs` pairs under the deterministic mode in force (256 when off)."""
+    return int(lib().peneo_pair_dz_fused_workspace_rows(int(npairs)))
+
+
 def pair_dz_args(D: int, classes: Sequence[int], dlogits: Sequence[torch.Tensor], w2: Sequence[torch.Tensor],
                  scale: torch.Tensor, drop_p: float = 0.0, drop_seed: int = 0, drop_doc: int = 0,
                  drop_pair0: int = 0) -> "hip.PairDzArgs":
@@ -1133,6 +1146,12 @@ def pair_dz_fused(ab_doc: torch.Tensor, i0: int, i1: int, wp: torch.Tensor, b1: 
     """dz [npairs, nh*D] of rows i0..i1 of one document straight from ab (bf16): no x / z round trip through memory.
     `x` / `pre` ([npairs, D], together) optionally receive what pair_x_fwd would write."""
     N, D2 = ab_doc.shape
+    if hip.deterministic_mode():     # a row per workgroup of the launch: the C call takes no size, a short workspace would be overrun
+        npairs = (i1 * N - i1 * (i1 - 1) // 2) - (i0 * N - i0 * (i0 - 1) // 2)
+        need = pair_dz_fused_workspace_rows(npairs) * 4 * args.num_heads * args.D
+        if not (workspace.dtype == torch.float32 and workspace.is_contiguous() and workspace.numel() >= need):
+            raise hip.PeneoHipError(f"pair_dz_fused: the workspace must hold {need} contiguous fp32 values under the deterministic "
+                                    f"mode in force (got {workspace.numel()}); size it with pair_dz_fused_workspace_rows")
     with kernel_timer("pair_dz_fused"):
         check(lib().peneo_pair_dz_fused(dtype_code(ab_doc.dtype), ptr(_c(ab_doc)), N, D2 // 2, i0, i1, ptr(wp), ptr(b1),
                                         C.byref(args), ptr(dz), ptr(workspace), ptr(x), ptr(pre), stream()),
@@ -1147,6 +1166,27 @@ def pair_bwd_supported(dtype: torch.dtype, D: int, num_heads: int = 0) -> bool:
 def pair_bwd_rows(N: int) -> int:
     """Rows per document of the dz / x buffers of ``pair_bwd_fused`` (pairs in 8 x 16 blocks of the triangle)."""
     return int(lib().peneo_pair_bwd_rows(N))
+
+
+def pair_bwd_workspace_rows(B: int, N: int) -> int:
+    """Rows of the dW2 / db1 workspace of ``pair_bwd_fused`` / ``pair_bwd_saved`` under the deterministic mode in force: 256 when
+    off, one per workgroup of the launch (B x blocks of the pair triangle) when on."""
+    return int(lib().peneo_pair_bwd_workspace_rows(B, N))
+
+
+def pair_bwd_workspace(B: int, N: int, nh: int, D: int, device) -> torch.Tensor:
+    """Zeroed [rows, 4 * nh * D] fp32 workspace of the fused pair backward, sized for the mode in force (pair_dz_finish sums it)."""
+    return torch.zeros((pair_bwd_workspace_rows(B, N), 4 * nh * D), dtype=torch.float32, device=device)
+
+
+def _check_pair_bwd_workspace(workspace: torch.Tensor, B: int, N: int, ncol: int) -> None:
+    """(the C call takes no size: with the mode on, a workspace sized for the default would be written out of bounds)"""
+    if not hip.deterministic_mode():
+        return
+    rows = pair_bwd_workspace_rows(B, N)
+    if not (workspace.dtype == torch.float32 and workspace.is_contiguous() and workspace.numel() >= rows * 4 * ncol):
+        raise hip.PeneoHipError(f"pair backward: the workspace must be contiguous fp32 [>= {rows}, {4 * ncol}] under the deterministic "
+                            f"mode in force (got {tuple(workspace.shape)} {workspace.dtype}); size it with pair_bwd_workspace")
 
 
 def pair_bwd_pack(w1: Sequence[torch.Tensor]) -> torch.Tensor:
@@ -1165,6 +1205,7 @@ def pair_bwd_fused(ab: torch.Tensor, wp: torch.Tensor, b1: torch.Tensor, args: "
     assert d_ab.dtype == torch.float32 and d_ab.shape == ab.shape and dz.dtype == x.dtype == torch.bfloat16
     rows = pair_bwd_rows(N)
     assert dz.shape[0] == B * rows and x.shape == (B * rows, D2 // 2)
+    _check_pair_bwd_workspace(workspace, B, N, args.num_heads * args.D)
     partials = torch.empty(lib().peneo_pair_bwd_partial_bytes(B, N, D2 // 2) // 4, dtype=torch.float32, device=ab.device)
     with kernel_timer("pair_bwd_fused"):
         check(lib().peneo_pair_bwd_fused(dtype_code(ab.dtype), ptr(_c(ab)), B, N, D2 // 2, ptr(wp), ptr(b1), C.byref(args),
@@ -1179,6 +1220,7 @@ def pair_bwd_saved(ab: torch.Tensor, wp: torch.Tensor, args: "hip.PairDzArgs", a
     B, N, D2 = ab.shape
     assert d_ab.dtype == torch.float32 and d_ab.shape == ab.shape and dz.dtype == torch.bfloat16
     assert dz.shape[0] == B * pair_bwd_rows(N)
+    _check_pair_bwd_workspace(workspace, B, N, args.num_heads * args.D)
     partials = torch.empty(lib().peneo_pair_bwd_partial_bytes(B, N, D2 // 2) // 4, dtype=torch.float32, device=ab.device)
     with kernel_timer("pair_bwd_saved"):
         check(lib().peneo_pair_bwd_saved(dtype_code(ab.dtype), ptr(_c(ab)), B, N, D2 // 2, ptr(wp), C.byref(args), ptr(act),

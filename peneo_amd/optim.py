@@ -82,6 +82,7 @@ class FusedAdamW(torch.optim.Optimizer):
         self._emit_into = emit_into
         self._emit, self._emit_plan, self._emitted = None, None, ()
         self._sqnorm = None
+        self._sq_ws = None
         self._tables = None
         self._step = 0
         self._entries = []
@@ -214,8 +215,15 @@ class FusedAdamW(torch.optim.Optimizer):
             if self._sqnorm is None or self._sqnorm.device != self._table.device:
                 self._sqnorm = torch.zeros(int(lib().peneo_grad_sqnorm_slots()), dtype=torch.float64, device=self._table.device)
             sq = self._sqnorm
-            check(lib().peneo_grad_sqnorm(ptr(self._table), ptr(self._chunk_t), ptr(self._chunk_i), self._chunk_t.numel(),
-                                          ptr(sq), stream()), "peneo_grad_sqnorm")
+            # deterministic mode: the chunks' sums go to a workspace and are added in chunk order (0 bytes and the plain call when off)
+            need = int(lib().peneo_grad_sqnorm_workspace_bytes(self._chunk_t.numel()))
+            ws = None
+            if need:
+                if self._sq_ws is None or self._sq_ws.numel() * 8 < need or self._sq_ws.device != self._table.device:
+                    self._sq_ws = torch.empty((need + 7) // 8, dtype=torch.float64, device=self._table.device)
+                ws = self._sq_ws
+            check(lib().peneo_grad_sqnorm_ws(ptr(self._table), ptr(self._chunk_t), ptr(self._chunk_i), self._chunk_t.numel(),
+                                             ptr(sq), ptr(ws), need, stream()), "peneo_grad_sqnorm_ws")
         if self._emit is None:
             check(lib().peneo_adamw_step_clip(ptr(self._table), ptr(self._chunk_t), ptr(self._chunk_i), self._chunk_t.numel(),
                                               float(g0["betas"][0]), float(g0["betas"][1]), float(g0["eps"]), self._step,
