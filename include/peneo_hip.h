@@ -396,6 +396,12 @@ typedef struct peneo_pair_heads_desc {
   uint32_t drop_seed;
 } peneo_pair_heads_desc;
 
+/* Host-side query (no GPU call, version 108): 1 where peneo_pair_heads_pack + peneo_pair_heads_fwd have a kernel for
+ * (dtype, D, num_heads), else 0.  D <= 512: D / 16 in {2, 4, 6, 8, 12, 16, 24, 32}, fp32 and bf16.  512 < D <= 1024: bf16 only, D a
+ * multiple of 64 (pair_heads_wide.hip: four waves of 32 pairs, a ring of two weight slabs; five heads fit at D = 1024, eight up to
+ * D = 960).  Everything else - fp32 above 512 among it - makes the two calls return PENEO_ERR_INVALID (and packed_bytes 0 above 512);
+ * a caller that needs such a width materialises the pair activations (peneo_pair_x_fwd + peneo_gemm). */
+int peneo_pair_heads_supported(int dtype, int D, int num_heads);
 size_t peneo_pair_heads_packed_bytes(int dtype, int num_heads, int D);
 /* w1[h] : [D, D] row-major fp32 (nn.Linear weight), w2[h] : [classes[h], D] fp32;
  * w1 / w2 / classes are HOST arrays (of device pointers / ints) with num_heads entries */

@@ -19,6 +19,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "pair_heads.h"
 #include <type_traits>
 
 namespace peneo {
@@ -28,7 +29,6 @@ namespace peneo {
 #endif
 constexpr int PH_WAVES = PH_WAVES_N;
 constexpr int PH_PAIRS = PH_WAVES * 32;   // pairs per workgroup (8 waves x 32)
-constexpr int NCP = 16;                   // padded class rows that are ever non-zero (<= 16)
 
 struct PackSrc {
   const float* w1[PENEO_MAX_HEADS];
@@ -46,7 +46,9 @@ struct PackSrc {
 // permutation is the one under which a C-layout accumulator tile is directly a B operand.
 // Slabs are padded to a whole number of 1 KiB DMA units per wave (slab_stride_elems elements per slab), so that
 // every wave of the forward kernel issues the same number of LDS-DMA instructions with immediate offsets.
+// (D > 512, bf16: the same slabs at the stride of the four-wave kernel, pair_heads.h: pair_wide_slab_bytes.)
 __host__ __device__ inline int64_t slab_stride_bytes(int D, int elem_bytes) {
+  if (D > 512) return pair_wide_slab_bytes(D);
   const int64_t payload = (int64_t)(D / 16 + 2) * 512 * elem_bytes;
   const int64_t quantum = (int64_t)PH_WAVES * 1024;
   return (payload + quantum - 1) / quantum * quantum;
@@ -82,35 +84,6 @@ __global__ void pack_weights_kernel(PackSrc s, T* out) {
     Elem<T>::store(out + j, v);
   }
 }
-
-struct PairFwdParams {
-  const void* ab; int B, N, D; int64_t P;
-  int num_heads; int classes[PENEO_MAX_HEADS]; int total_classes;
-  const void* wp; const float* b1; const float* b2;
-  float* logits[PENEO_MAX_HEADS];
-  const int64_t* tags[PENEO_MAX_HEADS];
-  const float* cw[PENEO_MAX_HEADS];
-  float* partials;   // [B * gridDim.x][32]: num[8] | den[8] | dl_sum[16] per workgroup
-  float* dlogits[PENEO_MAX_HEADS];
-  uint32_t drop_thr16, drop_seed; float drop_scale;   // K12 dropout (common.h: pair_drop_*): threshold 0 = off, scale = 1 / (1 - p)
-  // saving form (hand kernel only): the pairs are walked in the backward's blocks and the kernel leaves q / y records (common.h:
-  // PB_REC_BYTES) and x = SiLU(a_i + b_j) in block-row order for peneo_pair_bwd_saved; NULL = the plain walk, nothing saved
-  char* act; bf16_t* x_save; int ntiles;
-};
-
-constexpr float NEG_INF_F = -3.0e38f;
-// register arrays must only ever be indexed by compile-time constants (dynamic indices go to scratch)
-__device__ __forceinline__ float cls_at(const float (&cls)[NCP], int idx) {
-  float v = 0.f;
-#pragma unroll
-  for (int c = 0; c < NCP; ++c) v = (c == idx) ? cls[c] : v;
-  return v;
-}
-__device__ __forceinline__ void dls_add(float (&dls)[NCP], int idx, float g) {
-#pragma unroll
-  for (int c = 0; c < NCP; ++c) dls[c] += (c == idx) ? g : 0.f;
-}
-
 
 // s_waitcnt vmcnt(n) with a run-time (wave-uniform) n: the count must be an immediate
 __device__ __forceinline__ void wait_vmcnt(int n) {
@@ -1179,6 +1152,12 @@ static int launch_pair_fwd(const PairFwdParams& p, hipStream_t st) {
 
 template <typename T>
 static int dispatch_pair_fwd(const PairFwdParams& p, hipStream_t st) {
+  if (p.D > 512) {
+    // pair_heads_wide.hip: bf16 on four waves with the whole register file each; nothing for fp32 (its x fragments are twice as large)
+    if (sizeof(T) == 2 && !p.act && pair_wide_supported(PENEO_BF16, p.D, p.num_heads)) return pair_wide_fwd(p, st);
+    set_error("peneo_pair_heads_fwd: D=%d not supported (above 512: bf16 only, D a multiple of 64 up to 1024, no saving form)", p.D);
+    return PENEO_ERR_INVALID;
+  }
   switch (p.D / 16) {
     case 2: return launch_pair_fwd<T, 2>(p, st);
     case 4: return launch_pair_fwd<T, 4>(p, st);
@@ -1521,7 +1500,26 @@ static inline unsigned cap_blocks(int64_t n, int per = 256, int64_t cap = 8192) 
 }
 static int total_classes(const int* classes, int nh) { int t = 0; for (int h = 0; h < nh; ++h) t += classes[h]; return t; }
 
+// widths of pair_heads_fwd_kernel's instantiations (dispatch_pair_fwd)
+static bool pair_fwd_narrow_width(int D) {
+  switch (D % 16 == 0 ? D / 16 : 0) {
+    case 2: case 4: case 6: case 8: case 12: case 16: case 24: case 32: return true;
+    default: return false;
+  }
+}
+
+extern "C" int peneo_pair_heads_supported(int dtype, int D, int num_heads) {
+  if (!ok_dt(dtype) || num_heads < 1 || num_heads > PENEO_MAX_HEADS || D <= 0 || D % 32 != 0) return 0;
+  if (D > 512) return pair_wide_supported(dtype, D, num_heads) ? 1 : 0;
+  if (!pair_fwd_narrow_width(D)) return 0;
+  // the generic kernel's LDS (launch_pair_fwd_v): its ring of weight slabs and the b1 table
+  const size_t sh = (size_t)(dtype == PENEO_BF16 ? 3 : 2) * (size_t)slab_stride_bytes(D, dtype == PENEO_BF16 ? 2 : 4) +
+                    (size_t)num_heads * D * sizeof(float);
+  return sh <= 160 * 1024 ? 1 : 0;
+}
+
 extern "C" size_t peneo_pair_heads_packed_bytes(int dtype, int num_heads, int D) {
+  if (D > 512 && !pair_wide_supported(dtype, D, num_heads)) return 0;
   return (size_t)(num_heads * D / 32) * (size_t)slab_stride_bytes(D, dtype == PENEO_BF16 ? 2 : 4);
 }
 
@@ -1538,7 +1536,9 @@ extern "C" int peneo_pair_heads_pack(int dtype, const float* const* w1, const fl
     PENEO_REQUIRE(classes[h] >= 1 && classes[h] <= 4, "peneo_pair_heads_pack: classes[%d] must be 1..4", h);
     s.w1[h] = w1[h]; s.w2[h] = w2[h]; s.classes[h] = classes[h];
   }
-  const int64_t total = (int64_t)(num_heads * D / 32) * (slab_stride_bytes(D, dtype == PENEO_BF16 ? 2 : 4) / (dtype == PENEO_BF16 ? 2 : 4));
+  PENEO_REQUIRE(D <= 512 || pair_wide_supported(dtype, D, num_heads),
+                "peneo_pair_heads_pack: D=%d not supported (above 512: bf16 only, D a multiple of 64 up to 1024)", D);
+  const int64_t total =(int64_t)(num_heads * D / 32) * (slab_stride_bytes(D, dtype == PENEO_BF16 ? 2 : 4) / (dtype == PENEO_BF16 ? 2 : 4));
   if (dtype == PENEO_BF16) hipLaunchKernelGGL(pack_weights_kernel<bf16_t>, dim3(cap_blocks(total)), dim3(256), 0, (hipStream_t)stream, s, (bf16_t*)packed);
   else hipLaunchKernelGGL(pack_weights_kernel<float>, dim3(cap_blocks(total)), dim3(256), 0, (hipStream_t)stream, s, (float*)packed);
   return check_launch("peneo_pair_heads_pack");

@@ -153,6 +153,7 @@ SIGNATURES = {
     "peneo_attn2_bwd_workspace_bytes": (_sz, [_i, _i, _i]),
     "peneo_attn2_bwd": (_i, [_i, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i, _i, _i, _i, _i,
                              _f, _f, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _f, _vp, _vp]),
+    "peneo_pair_heads_supported": (_i, [_i, _i, _i]),
     "peneo_pair_heads_packed_bytes": (_sz, [_i, _i, _i]),
     "peneo_pair_heads_pack": (_i, [_i, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "peneo_pair_heads_fwd": (_i, [_i, _vp, _i, _i, C.POINTER(PairHeadsDesc), _vp, C.POINTER(PairLoss), _vp]),

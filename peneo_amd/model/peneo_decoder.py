@@ -242,11 +242,14 @@ class _DecoderStage(torch.autograd.Function):
         bab = wc.cat_vec("dec.bab", [None, wc_b], [wc_b.numel(), wc_b.numel()])      # (zeros | bias)
         ab = ops.gemm(h, Wab, bias=bab).view(B, N, 2 * D)
         cws = [dec.le_loss.weight] + [dec.link_loss.weight] * 4 if tags is not None else None
-        if kcls != 2:
-            # classifier depths other than the shipped 2 (reference :253-271): materialising per-document path
+        if not dec.fused_pair_heads(dt, D):
+            # classifier depths other than the shipped 2 (reference :253-271) and widths without a fused pair-heads kernel (shrink off:
+            # fp32 above 512, any D / 16 outside the kernels' list): materialising per-document path
+            if kcls == 2 and tags is not None and dec.le_loss.ohem:
+                raise ValueError(f"OHEM runs behind the fused pair-heads kernel only, and there is none for {dt} at D = {D}")
             logits, outs, extra = _generic_heads_forward(dec, ab, heads, tags, cws, seeds, need_grad, want_logits)
             saved.update(extra)
-            saved.update(ab=ab, B=B, N=N, D=D, seq=seq)
+            saved.update(ab=ab, B=B, N=N, D=D, seq=seq, generic_heads=True)
             ctx.dec, ctx.saved, ctx.params = dec, saved, params
             ctx.has_loss = tags is not None
             ctx.mark_non_differentiable(*[lg for lg in logits if lg is not None])
@@ -368,7 +371,7 @@ class _DecoderStage(torch.autograd.Function):
             extra = torch.stack([d.to(torch.float32).reshape(()) if d is not None else torch.zeros((), device=dev)
                                  for d in d_heads])
             scale = scale + extra * sv["inv_den"]
-        if kcls != 2:
+        if sv.get("generic_heads"):   # (what the forward ran: fused_pair_heads reads a switch that may have changed since)
             d_ab, head_grads = _generic_heads_backward(dec, sv, heads, scale)
             return _DecoderStage._front_backward(ctx, dec, sv, params, d_ab, head_grads)
         w1s, b1s = [hd[0] for hd in heads], [hd[1] for hd in heads]
@@ -743,6 +746,7 @@ class PEneoDecoder(nn.Module):
         self.fused_dz = os.environ.get("PENEO_DZ_FUSED", "1") != "0"            # bf16: dz without x / z in memory
         self.fused_bwd = os.environ.get("PENEO_BWD_FUSED", "1") != "0"          # bf16: the whole pair-space backward in one kernel
         self.save_pair_act = os.environ.get("PENEO_PAIR_SAVE", "1") != "0"      # D = 384: the forward saves the classifiers' pre-activations
+        self.pair_wide = os.environ.get("PENEO_PAIR_WIDE", "1") != "0"          # bf16, 512 < D <= 1024: the fused four-wave forward
         self.dw1_on_side = os.environ.get("PENEO_DW1_SIDE", "1") != "0"          # its dW1 GEMM beside the following stages
         self.dw1_hold = os.environ.get("PENEO_DW1_HOLD", "1") != "0"             # ... joined at the end of the backward only
         self.dw1_side_split = int(os.environ.get("PENEO_DW1_SPLIT", "0"))   # fixed split-k of that GEMM; 0: from the targets below
@@ -784,6 +788,14 @@ class PEneoDecoder(nn.Module):
             if not (self.save_pair_act and self.fused_bwd):
                 raise ValueError("the mxfp8 train format of the pair heads feeds the saved backward: save_pair_act and fused_bwd must be on")
         self.pair_heads_train_format = fmt
+
+    def fused_pair_heads(self, dt: torch.dtype, D: int) -> bool:
+        """True where the forward runs the fused pair-heads kernel: the 2-layer classifiers at a (dtype, width) the library has one
+        for.  Everything else takes the materialising per-document path, forward and backward.  Above 512 (bf16, the four-wave
+        kernel of pair_heads_wide.hip) ``pair_wide`` / PENEO_PAIR_WIDE=0 switches the fused kernel off: the A/B arm."""
+        if self.num_cls_layers != 2 or not ops.pair_heads_supported(dt, D, len(HEAD_NAMES)):
+            return False
+        return D <= 512 or self.pair_wide
 
     def stacked_combine_weight(self, wc_w: torch.Tensor, dt: torch.dtype) -> torch.Tensor:
         """[Wc[:, :D]; Wc[:, D:]] as a [2D, D] working-precision matrix, so one GEMM yields [a | b]."""

@@ -799,11 +799,18 @@ def _ptr_list(ts: Sequence[Optional[torch.Tensor]]):
     return arr
 
 
+def pair_heads_supported(dtype, D: int, num_heads: int) -> bool:
+    """True where pair_heads_pack / pair_heads_fwd have a kernel for this dtype, width and head count (host-side query)."""
+    return bool(lib().peneo_pair_heads_supported(dtype_code(dtype), int(D), int(num_heads)))
+
+
 def pair_heads_pack(dtype: torch.dtype, w1: Sequence[torch.Tensor], w2: Sequence[torch.Tensor]) -> torch.Tensor:
     """w1[h]: [D, D] fp32, w2[h]: [C_h, D] fp32 -> one packed byte buffer (both layers, MFMA fragment order)."""
     nh, D = len(w1), w1[0].shape[1]
     dc = dtype_code(dtype)
     dev = w1[0].device
+    if D > 512 and not pair_heads_supported(dtype, D, nh):   # (no packed image exists: peneo_pair_heads_packed_bytes is 0)
+        raise hip.PeneoHipError(f"peneo_pair_heads_pack: D={D} not supported for {dtype} with {nh} heads (pair_heads_supported)")
     packed = torch.empty(lib().peneo_pair_heads_packed_bytes(dc, nh, D), dtype=torch.uint8, device=dev)
     classes = (C.c_int * nh)(*[w.shape[0] for w in w2])
     check(lib().peneo_pair_heads_pack(dc, _ptr_list([_c(w) for w in w1]), _ptr_list([_c(w) for w in w2]), classes, nh, D,
