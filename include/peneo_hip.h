@@ -444,6 +444,30 @@ int peneo_pair_heads_fwd_save(int dtype, const void* ab, int B, int N, const pen
                               float* const* logits, const peneo_pair_loss* loss, void* act, void* x_rows,
                               peneo_stream_t stream);
 
+/* The e4m3 form of the saved activations (version 109, opt-in): the same launch - same walk, same arithmetic, same K12 dropout; logits,
+ * loss partial rows, dlogits and x_rows are the bytes peneo_pair_heads_fwd_save writes - with one byte per pair and hidden unit in `act`:
+ *   act    [peneo_pair_save_e4m3_bytes(B, N, num_heads, D)] = half of peneo_pair_save_bytes: per document, block, 32-unit slab and
+ *          group of 32 pairs (the order of the f16 form) one 1 KiB record of 32 x 32 e4m3fn bytes.
+ * VALUE: each byte is e4m3fn(RNE(clamp(v, -448, 448))) of the f16 value v peneo_pair_heads_fwd_save stores for that pair and unit (a
+ *   conversion of the f16 value, not of the fp32 accumulator: no double rounding to allow for).  The clamp is explicit in the kernel.  A
+ *   dropped unit (-30000 + W1 x in the f16 form) is therefore -448: sigmoid(-448) is exactly 0 in the backward's fp32 arithmetic (exp2
+ *   overflows to +inf, its reciprocal is 0), so y = 0 and SiLU' = 0 with no mask, as in the f16 form.
+ * RANGE: a kept |z| above 448 saturates to +-448: the backward's result for that unit is finite and off by the excess, never NaN.
+ *   Pre-activations are O(10) with LayerNorm-ed inputs; the f16 form's bound (|W1 x + b1| < 30000) applies unchanged.
+ * LAYOUT of a record: [16 rows][64 bytes].  Pair p = 8 qd + 4 h + e of the group (qd = 0..3, h = 0..1, e = 0..3) is in row
+ *   8 (qd >> 1) + 4 h + 2 (qd & 1) + (e >> 1); a row holds, per hidden unit, the two bytes (pair with e even, pair with e odd), and the
+ *   32 units of the slab stand in the row as eight-byte quads: units 8 G + 4 f + 0..3 (G = 0..3, f = 0..1) at byte 16 (2 (G >> 1) + f)
+ *   + 8 (G & 1).  (The backward's transposing LDS read moves 16-bit elements: a two-pair element per unit gives every lane eight pairs
+ *   of its unit per read, and the four rows a read touches are 256 consecutive bytes.)
+ * peneo_pair_save_e4m3_supported: host-side query (no GPU call), 1 exactly where peneo_pair_save_supported is 1 (bf16, D = 384).
+ * Returns PENEO_ERR_INVALID with a peneo_last_error() text for an unsupported (dtype, D, heads), a NULL act / x_rows or a buffer that is
+ * not 16-byte aligned.  The MXFP8 train forward (peneo_pair_heads_fwd_mxfp8_save) keeps writing f16 records. */
+int peneo_pair_save_e4m3_supported(int dtype, int D, int num_heads);
+size_t peneo_pair_save_e4m3_bytes(int B, int N, int num_heads, int D);
+int peneo_pair_heads_fwd_save_e4m3(int dtype, const void* ab, int B, int N, const peneo_pair_heads_desc* desc,
+                                   float* const* logits, const peneo_pair_loss* loss, void* act, void* x_rows,
+                                   peneo_stream_t stream);
+
 /* MXFP8 inference form of the same heads (pair_heads_mx.hip; eval only: no dropout, no dlogits, no backward).
  * Both first-layer operands, the rows of W1cat [num_heads * D, D] and every pair's x = SiLU(a_i + b_j) (fp32 from the bf16 `ab`),
  * are quantized to OCP MX v1.0 MXFP8: per block of 32 consecutive elements along D, scale 2^e with e = floor(log2(amax)) - 8
@@ -603,6 +627,15 @@ int peneo_pair_bwd_fused(int dtype, const void* ab, int B, int N, int D, const v
 int peneo_pair_bwd_saved(int dtype, const void* ab, int B, int N, int D, const void* w_packed,
                          const peneo_pair_dz_args* args, const void* act, void* dz, float* d_ab, float* workspace,
                          float* partials, peneo_stream_t stream);
+
+/* peneo_pair_bwd_saved on the 1 KiB e4m3 records of peneo_pair_heads_fwd_save_e4m3 (version 109): the same launch with one LDS-DMA piece
+ * per slab and group instead of two and a 16 KiB record ring instead of 32.  A value is decoded e4m3 -> fp32 (exact) and then goes
+ * through the statements the f16 form runs on its f16 -> fp32 value: on records that hold the same values the two give the same dz and
+ * d_ab bit for bit.  Same arguments, same workspace rows (peneo_pair_bwd_workspace_rows), same deterministic mode: a row per workgroup
+ * under peneo_set_deterministic(1 / 2), and in the default mode the call counts in peneo_order_dependent_launches as the f16 form does. */
+int peneo_pair_bwd_saved_e4m3(int dtype, const void* ab, int B, int N, int D, const void* w_packed,
+                              const peneo_pair_dz_args* args, const void* act, void* dz, float* d_ab, float* workspace,
+                              float* partials, peneo_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * K13 — loss finish: reduces the per-workgroup partial rows of peneo_pair_heads_fwd:
@@ -832,7 +865,7 @@ void peneo_gemm_sk_set_max_groups(int n);
  * PENEO_DETERMINISTIC = 0 / 1 / 2 sets the initial value.  Under modes 1 and 2 two executions of the same calls on the same inputs,
  * in one process on one device, give the same bits.  Nothing is claimed across devices, processes, ranks, batch sizes or builds.
  * Forms: peneo_colsum, peneo_layernorm_bwd and peneo_embed_text_bwd switch to single-writer kernels inside their
- * launchers (no workspace; peneo_encoder_layer_bwd follows through them); peneo_pair_bwd_fused / peneo_pair_bwd_saved give every
+ * launchers (no workspace; peneo_encoder_layer_bwd follows through them); peneo_pair_bwd_fused / peneo_pair_bwd_saved(_e4m3) give every
  * workgroup a workspace row of its own, and so does peneo_pair_dz_fused; peneo_pair_x_bwd runs one workgroup per row; the
  * relative-position tables and the gradient norm take a workspace through the _ws entry points below.  Order-dependent in every
  * mode (counted; refused under 2): peneo_gemm with a_colsum or pair_dz, peneo_attn_bwd with dq_accum, peneo_ohem_ce,
@@ -842,7 +875,7 @@ void peneo_gemm_sk_set_max_groups(int n);
 void peneo_set_deterministic(int mode);
 int peneo_deterministic(void);
 uint64_t peneo_order_dependent_launches(void);
-/* Workspace rows of peneo_pair_bwd_fused / peneo_pair_bwd_saved under the mode in force: [rows][4 * num_heads * D] fp32, zeroed by
+/* Workspace rows of peneo_pair_bwd_fused / peneo_pair_bwd_saved(_e4m3) under the mode in force: [rows][4 * num_heads * D] fp32, zeroed by
  * the caller, summed afterwards with peneo_colsum.  Mode 0: 256.  Modes 1 / 2: one row per workgroup of the launch, B * (blocks of
  * the pair triangle) = B * peneo_pair_bwd_rows(N) / 128 - at 8 x 511 tokens 8 448 rows x 4 * 5 * 384 floats = 260 MB.  Size the
  * workspace under the mode the call runs with. */

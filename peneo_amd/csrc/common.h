@@ -295,6 +295,33 @@ __host__ __device__ inline int pb_num_tiles(int N) { return pb_tiles_before(pb_r
 // unit's as -30000 (the K12 dropout; SiLU and SiLU' of that are 0).  Record = [2 halves of 16 units][32 pairs][16 units]: 32-byte
 // rows in the group's pair order, the rows of the second half stored at pair ^ 4 (bank spread of the backward's transposing reads)
 constexpr int PB_REC_BYTES = 2048;
+// The e4m3 form of the same records (peneo_pair_heads_fwd_save_e4m3 -> peneo_pair_bwd_saved_e4m3), 1 KiB each, in the same order: every
+// value is e4m3fn(RNE(clamp(v, -448, 448))) of the f16 value v of the record above, so a dropped unit's is -448 (sigmoid(-448) is
+// exactly 0 in the backward's fp32 arithmetic: y = 0 and SiLU' = 0 with no mask, as with -30000) and a kept |z| above 448 saturates:
+// finite, off by the excess, never NaN.  Record = [16 rows][64 bytes]; a row holds two pairs 2m, 2m + 1 of the group, a 2-byte element
+// (pair 2m, pair 2m + 1) per unit, so that one ds_read_b64_tr_b16 hands a lane eight pairs of ITS unit (the transposing read moves
+// 16-bit elements: a byte pair that belongs to one unit stays with its lane).  Pair p = 8 qd + 4 h + e sits in row pb_rec8_row(p) =
+// 8 (qd >> 1) + 4 h + 2 (qd & 1) + (e >> 1), byte e & 1 of its element: the four rows a 16-lane group reads together (pairs 8 qd + 4 h +
+// 0..3 for two qd) are four consecutive rows = 256 bytes, all banks once.  Inside a row the eight-byte quad of units 8 G + 4 hf + 0..3
+// stands at byte 16 (2 (G >> 1) + hf) + 8 (G & 1): the sixteen bytes a forward lane (pair parity G >> 1, half hf) holds after one
+// exchange with the neighbouring pair's lane, so every store instruction of the forward writes 1 KiB contiguous.
+constexpr int PB_REC8_BYTES = 1024;
+__host__ __device__ inline int pb_rec8_row(int pair) { return 8 * (pair >> 4) + 4 * ((pair >> 2) & 1) + 2 * ((pair >> 3) & 1) + ((pair >> 1) & 1); }
+// four f16 values (two packed dwords) -> four e4m3fn bytes, clamped to +-448 first (v_pk_max_f16 / v_pk_min_f16 take the bound from
+// a scalar register: VOP3P has no literal operand on gfx9)
+__device__ __forceinline__ uint32_t pack_e4m3x4_clamped(uint32_t h01, uint32_t h23) {
+  typedef _Float16 pe_h2 __attribute__((ext_vector_type(2)));
+  typedef short pe_s2 __attribute__((ext_vector_type(2)));
+  // (asm: the builtin min / max come with a canonicalising v_pk_max_f16 x, x each; 0x5F00 = 448 in f16)
+  const uint32_t lo = 0xDF00DF00u, hi = 0x5F005F00u;
+  uint32_t a, c;
+  asm("v_pk_max_f16 %0, %1, %2\n\tv_pk_min_f16 %0, %0, %3" : "=&v"(a) : "v"(h01), "s"(lo), "s"(hi));
+  asm("v_pk_max_f16 %0, %1, %2\n\tv_pk_min_f16 %0, %0, %3" : "=&v"(c) : "v"(h23), "s"(lo), "s"(hi));
+  pe_s2 r = {0, 0};
+  r = __builtin_amdgcn_cvt_scalef32_pk_fp8_f16(r, __builtin_bit_cast(pe_h2, a), 1.0f, false);
+  r = __builtin_amdgcn_cvt_scalef32_pk_fp8_f16(r, __builtin_bit_cast(pe_h2, c), 1.0f, true);
+  return __builtin_bit_cast(uint32_t, r);
+}
 
 // ---------------------------------------------------------------- LDS-DMA (global -> LDS without VGPRs)
 __device__ __forceinline__ uint32_t lds_addr(const void* p) {

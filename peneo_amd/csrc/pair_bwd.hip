@@ -738,6 +738,11 @@ __device__ __forceinline__ void pb_mma_acc(const pb_u32x4& a, const pb_u32x4& b,
 // vm counter: the producers only ever have record pieces in flight (2 per slab: all loads, in order -> vmcnt(4) = "slab s has
 // landed"); the consumers have weight pieces (6 per wave and slab), the dz row stores and the flush atomics: loads and writes may
 // retire out of order with each other, so the count that proves "the 6 pieces of slab s-1 are in" is 6.
+// E4M3 (peneo_pair_bwd_saved_e4m3): the records are the 1 KiB e4m3 form (common.h: PB_REC8_BYTES).  Only the record request, the record
+// read with its decode, and the counts differ: ONE piece per slab, so the producers' vm counter still sees record pieces only and
+// vmcnt(PSV_NR - 2) = vmcnt(2) = "slab s has landed"; the ring is PSV_NR x 4 KiB = 16 KiB instead of 32; two transposing reads per
+// slab instead of four (a 16-bit element = two pairs of the lane's unit), and a value is e4m3 -> fp32 (v_cvt_pk_f32_fp8, exact) where
+// the f16 form converts f16 -> fp32 (exact): what follows is the same statements on the same fp32 values.
 // ================================================================================================
 #ifndef PSV_NR
 #define PSV_NR 4        // record ring slots (requests run PSV_NR - 1 slabs ahead)
@@ -745,9 +750,11 @@ __device__ __forceinline__ void pb_mma_acc(const pb_u32x4& a, const pb_u32x4& b,
 #ifndef PSV_SPREAD
 #define PSV_SPREAD 0    // 1: a consumer's weight pieces go out one per chunk instead of all behind the first reads
 #endif
-template <int KS, bool DROP>
+template <int KS, bool DROP, bool E4M3 = false>
 __global__ __launch_bounds__(PW_WAVES * 64, 2) void pair_bwd_sv_kernel(PairBwdParams p) {
   using T = bf16_t;
+  constexpr int REC_BYTES = E4M3 ? PB_REC8_BYTES : PB_REC_BYTES;
+  constexpr int REC_PIECES = REC_BYTES / 1024;               // LDS-DMA pieces per record
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int HALF_BYTES = KS * 1024;
   constexpr int NDT = KS / 2;
@@ -759,8 +766,8 @@ __global__ __launch_bounds__(PW_WAVES * 64, 2) void pair_bwd_sv_kernel(PairBwdPa
   const int grp = wave & 3;
   const int D = p.D, N = p.N, nh = p.a.num_heads, ncol = nh * D;
   char* sA = smem;                                                          // [3][HALF_BYTES] weight ring: slab s in slot s % 3
-  char* sR = smem + 3 * HALF_BYTES;                                         // [PSV_NR][4 groups][PB_REC_BYTES] record ring: slab s in slot s % PSV_NR
-  uint2* sW2p = reinterpret_cast<uint2*>(sR + PSV_NR * 4 * PB_REC_BYTES);   // [ncol]: the column's W2 rows as bf16 (w0, w1 | w2, 0)
+  char* sR = smem + 3 * HALF_BYTES;                                         // [PSV_NR][4 groups][REC_BYTES] record ring: slab s in slot s % PSV_NR
+  uint2* sW2p = reinterpret_cast<uint2*>(sR + PSV_NR * 4 * REC_BYTES);   // [ncol]: the column's W2 rows as bf16 (w0, w1 | w2, 0)
   float4* sG = reinterpret_cast<float4*>(sW2p + ncol);                      // [4][32]
   float4* sPart = sG + 4 * 32;                                              // [2][4][32]
   char* sT = reinterpret_cast<char*>(sPart + 2 * 4 * 32);                   // [2][4][32 rows][64 B]
@@ -812,12 +819,12 @@ __global__ __launch_bounds__(PW_WAVES * 64, 2) void pair_bwd_sv_kernel(PairBwdPa
       }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // from here on this wave's vm counter only sees its record pieces
-    // record of slab s: 2 pieces of 1 KiB into slot s & 3
-    const char* rsrc = p.act + ((((int64_t)b * p.ntiles + blockIdx.x) * nslab * 4 + grp) * PB_REC_BYTES) + lane * 16;
+    // record of slab s: REC_PIECES pieces of 1 KiB (f16: 2, e4m3: 1) into slot s & 3
+    const char* rsrc = p.act + ((((int64_t)b * p.ntiles + blockIdx.x) * nslab * 4 + grp) * REC_BYTES) + lane * 16;
     auto request = [&](int s, int slot) {
-      const char* src = rsrc + (int64_t)min(s, nslab - 1) * (4 * PB_REC_BYTES);     // (past the end: the last slab again, into a free slot)
-      const uint32_t dst = __builtin_amdgcn_readfirstlane(recs + (slot * 4 + grp) * PB_REC_BYTES);
-      if constexpr (!(PB_ABLATE & 16)) { lds_dma_1k<0>(src, dst); lds_dma_1k<1024>(src, dst); }
+      const char* src = rsrc + (int64_t)min(s, nslab - 1) * (4 * REC_BYTES);     // (past the end: the last slab again, into a free slot)
+      const uint32_t dst = __builtin_amdgcn_readfirstlane(recs + (slot * 4 + grp) * REC_BYTES);
+      if constexpr (!(PB_ABLATE & 16)) { lds_dma_1k<0>(src, dst); if constexpr (!E4M3) lds_dma_1k<1024>(src, dst); }
     };
 #pragma unroll
     for (int k = 0; k < PSV_NR - 1; ++k) request(k, k);
@@ -849,23 +856,28 @@ __global__ __launch_bounds__(PW_WAVES * 64, 2) void pair_bwd_sv_kernel(PairBwdPa
     // transposing reads of a record (two 1 KiB halves hg of 16 units, 32-byte rows, the second half's rows at pair ^ 4: common.h): the
     // 16-lane group (hg = (lane >> 4) & 1, half) supplies, for quad qd, rows 8 qd + 4 half + r (r = (lane & 15) >> 2), units 16 hg + 4 c ..
     // + 3 (c = lane & 3) and receives pairs 8 qd + 4 half + 0..3 of unit 16 hg + (lane & 15) = lane & 31
-    const uint32_t tr_l = (uint32_t)(((lane >> 4) & 1) * 1024 + ((4 * (half ^ ((lane >> 4) & 1)) + ((lane & 15) >> 2)) * 32) + (lane & 3) * 8);
+    // e4m3 records ([16 rows][64 bytes], common.h): the group (hg, half) supplies, for read R, rows 8 R + 4 half + q (q = (lane & 15) >> 2:
+    // pairs 8 (2 R + (q >> 1)) + 4 half + 2 (q & 1), + 1) and there the quad of units 16 hg + 4 c .. + 3 (c = lane & 3), which stands at byte
+    // 16 (2 hg + (c & 1)) + 8 (c >> 1); it receives, for its unit, dword qd = 2 R + {0, 1} = the bytes of pairs 8 qd + 4 half + 0..3
+    const uint32_t tr_l = E4M3 ? (uint32_t)((4 * half + ((lane & 15) >> 2)) * 64 + 16 * (2 * ((lane >> 4) & 1) + (lane & 1)) + 8 * ((lane >> 1) & 1))
+                               : (uint32_t)(((lane >> 4) & 1) * 1024 + ((4 * (half ^ ((lane >> 4) & 1)) + ((lane & 15) >> 2)) * 32) + (lane & 3) * 8);
     const uint32_t tbase = lds_addr(sT) + grp * 2048 + half * 256 + ((2 * r32) & 15);
     const uint32_t tA0 = tbase + ((((r32 >> 3) ^ half)) << 4), tB0 = tbase + ((((r32 >> 3) ^ half ^ 2)) << 4);
     const float nl2e = -1.4426950408889634f;
     __syncthreads();                                          // sW2p visible (matches the consumers' barrier)
     int rslot = 0;                                            // s % PSV_NR
     for (int s = 0; s < nslab; ++s) {
-      top(std::integral_constant<int, 2 * (PSV_NR - 2)>{});   // record s has landed (records s + 1 .. s + PSV_NR - 2 may be on their way)
+      top(std::integral_constant<int, REC_PIECES * (PSV_NR - 2)>{});   // record s has landed (records s + 1 .. s + PSV_NR - 2 may be on their way)
       request(s + PSV_NR - 1, rslot == 0 ? PSV_NR - 1 : rslot - 1);   // slot (s - 1) % PSV_NR: last read by E(s - 1)
       if (s % spb == 0) stage_g(s / spb);
       const uint2 cw2 = sW2p[s * 32 + r32];
-      const uint32_t ra = recs + (rslot * 4 + grp) * PB_REC_BYTES + tr_l;
+      const uint32_t ra = recs + (rslot * 4 + grp) * REC_BYTES + tr_l;
       rslot = rslot == PSV_NR - 1 ? 0 : rslot + 1;
       pb_u32x2 zv[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) asm volatile("" : "=v"(zv[i]));
-      pb_trd<0>(zv[0], ra); pb_trd<256>(zv[1], ra); pb_trd<512>(zv[2], ra); pb_trd<768>(zv[3], ra);
+      if constexpr (E4M3) { pb_trd<0>(zv[0], ra); pb_trd<512>(zv[1], ra); }
+      else { pb_trd<0>(zv[0], ra); pb_trd<256>(zv[1], ra); pb_trd<512>(zv[2], ra); pb_trd<768>(zv[3], ra); }
       f32x16_t dy, acc;
 #pragma unroll
       for (int r = 0; r < 16; ++r) { dy[r] = 0.f; acc[r] = 0.f; }
@@ -880,13 +892,21 @@ __global__ __launch_bounds__(PW_WAVES * 64, 2) void pair_bwd_sv_kernel(PairBwdPa
       pb_static_for<8>([&](auto jc) {
         constexpr int J = decltype(jc)::value;
         constexpr int r0 = 2 * J, rowc = (r0 & 3) + 8 * (r0 >> 2);
-        const uint32_t zw2 = (J & 1) ? zv[J >> 1].y : zv[J >> 1].x;  // registers r0, r0 + 1 = halves (lo, hi) of dword J of the 16 saved values
+        // f16: registers r0, r0 + 1 = halves (lo, hi) of dword J of the 16 saved values; e4m3: bytes 2 (J & 1), + 1 of dword J >> 1 of the four
+        const uint32_t zw2 = E4M3 ? ((J & 2) ? zv[J >> 2].y : zv[J >> 2].x) : ((J & 1) ? zv[J >> 1].y : zv[J >> 1].x);
         // (plain C++, compiled to v_fma_mix_f32: the compiler then also places the wait states between the dy MFMA and its first reader -
         // an inline-asm reader gets none and read zeros for rows 0, 1)
-        const f16x2_t zh = __builtin_bit_cast(f16x2_t, zw2);
-        const float t0 = __builtin_fmaf((float)zh[0], nl2e, 0.f), t1 = __builtin_fmaf((float)zh[1], nl2e, 0.f);
+        float zf0, zf1;
+        if constexpr (E4M3) {
+          const auto zf = __builtin_amdgcn_cvt_pk_f32_fp8((int)zw2, (J & 1) != 0);
+          zf0 = zf[0]; zf1 = zf[1];
+        } else {
+          const f16x2_t zh = __builtin_bit_cast(f16x2_t, zw2);
+          zf0 = (float)zh[0]; zf1 = (float)zh[1];
+        }
+        const float t0 = __builtin_fmaf(zf0, nl2e, 0.f), t1 = __builtin_fmaf(zf1, nl2e, 0.f);
         const float sg0 = (PB_ABLATE & 8) ? t0 : __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(t0) + 1.f), sg1 = (PB_ABLATE & 8) ? t1 : __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(t1) + 1.f);
-        const float y0 = __builtin_fmaf((float)zh[0], sg0, 0.f), y1 = __builtin_fmaf((float)zh[1], sg1, 0.f);
+        const float y0 = __builtin_fmaf(zf0, sg0, 0.f), y1 = __builtin_fmaf(zf1, sg1, 0.f);
         // SiLU'(z) = sg (1 + z (1 - sg)) = (sg + y) - y sg
         const float d0 = dy[r0] * fmaf(-y0, sg0, sg0 + y0), d1 = dy[r0 + 1] * fmaf(-y1, sg1, sg1 + y1);
         yv[r0] = y0; yv[r0 + 1] = y1;
@@ -1010,6 +1030,12 @@ __global__ __launch_bounds__(PW_WAVES * 64, 2) void pair_bwd_sv_kernel(PairBwdPa
     }
     __syncthreads();     // every wave is done with the rings
     // ---- du * SiLU'(a_i + b_j): sums over j stay in the wave, sums over i meet in LDS (the rings are dead) ----
+    // red is 4 * NDT * 2 KiB = 96 KiB at KS = 24.  The f16 form's rings (72 + 32 KiB) hold it; the e4m3 form's (72 + 16 KiB) do not:
+    // there it runs 8 KiB into sW2p (with few heads on into sG / sPart / sT).  All of those are dead as well: the producers read sW2p
+    // and sG and write sPart / sT inside their slab loop only, the consumers read sPart / sT in U(nslab - 1) at the latest, and every
+    // wave has passed the barrier above since.  The launch's LDS (launch_pair_bwd_sv) covers red in both forms, whatever the head count:
+    static_assert((size_t)4 * NDT * 16 * 32 * sizeof(float) <= (size_t)3 * HALF_BYTES + PSV_NR * 4 * REC_BYTES + 4 * 32 * 16 * 3 + 2 * 4 * 2048,
+                  "the consumers' reduction buffer must fit the LDS of a launch even with an empty W2 table");
     float* red = reinterpret_cast<float*>(smem);                      // [4][NDT][16][32]
     const int ia = min(i0, N - 1), ib = min(i0 + 1, N - 1);
     float* pa = p.part_a + (((int64_t)b * p.ntiles + blockIdx.x) * PB_TI + 2 * grp + half) * D;
@@ -1563,17 +1589,18 @@ static int launch_pair_bwd_ws(const PairBwdParams& p, hipStream_t st) {
   return check_launch("peneo_pair_bwd_fused");
 }
 
-template <int KS, bool DROP>
+template <int KS, bool DROP, bool E4M3 = false>
 static int launch_pair_bwd_sv(const PairBwdParams& p, hipStream_t st) {
   const int ncol = p.a.num_heads * p.D;
-  const size_t sh = (size_t)3 * KS * 1024 + (size_t)PSV_NR * 4 * PB_REC_BYTES + (size_t)ncol * 8 + (size_t)4 * 32 * 16 * 3 + (size_t)2 * 4 * 2048;
-  if (sh > 160 * 1024) { set_error("peneo_pair_bwd_saved: D=%d with %d heads needs %zu bytes of LDS", p.D, p.a.num_heads, sh); return PENEO_ERR_INVALID; }
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(pair_bwd_sv_kernel<KS, DROP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh) != hipSuccess) {
-    set_error("peneo_pair_bwd_saved: cannot raise dynamic LDS to %zu bytes", sh);
+  constexpr const char* who = E4M3 ? "peneo_pair_bwd_saved_e4m3" : "peneo_pair_bwd_saved";
+  const size_t sh = (size_t)3 * KS * 1024 + (size_t)PSV_NR * 4 * (E4M3 ? PB_REC8_BYTES : PB_REC_BYTES) + (size_t)ncol * 8 + (size_t)4 * 32 * 16 * 3 + (size_t)2 * 4 * 2048;
+  if (sh > 160 * 1024) { set_error("%s: D=%d with %d heads needs %zu bytes of LDS", who, p.D, p.a.num_heads, sh); return PENEO_ERR_INVALID; }
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(pair_bwd_sv_kernel<KS, DROP, E4M3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh) != hipSuccess) {
+    set_error("%s: cannot raise dynamic LDS to %zu bytes", who, sh);
     return PENEO_ERR_LAUNCH;
   }
-  hipLaunchKernelGGL((pair_bwd_sv_kernel<KS, DROP>), dim3((unsigned)p.ntiles, (unsigned)p.B), dim3(PW_WAVES * 64), sh, st, p);
-  return check_launch("peneo_pair_bwd_saved");
+  hipLaunchKernelGGL((pair_bwd_sv_kernel<KS, DROP, E4M3>), dim3((unsigned)p.ntiles, (unsigned)p.B), dim3(PW_WAVES * 64), sh, st, p);
+  return check_launch(who);
 }
 
 template <int KS>
@@ -1635,32 +1662,48 @@ extern "C" int64_t peneo_pair_bwd_workspace_rows(int B, int N) {
   return det_mode() >= 1 ? (int64_t)B * pb_num_tiles(N) : (int64_t)PB_SLOTS;
 }
 
-extern "C" int peneo_pair_bwd_saved(int dtype, const void* ab, int B, int N, int D, const void* w_packed,
-                                    const peneo_pair_dz_args* args, const void* act, void* dz, float* d_ab, float* workspace,
-                                    float* partials, peneo_stream_t stream) {
-  PENEO_REQUIRE(args && peneo_pair_save_supported(dtype, D, args->num_heads), "peneo_pair_bwd_saved: bf16, D = 384 only (peneo_pair_save_supported)");
-  PENEO_REQUIRE(ab && w_packed && act && dz && d_ab && workspace && partials && B > 0 && N > 0, "peneo_pair_bwd_saved: bad arguments");
-  PENEO_REQUIRE(args->D == D && args->scale && args->num_heads * D >= 64, "peneo_pair_bwd_saved: bad head description");
+static int pair_bwd_saved_impl(int dtype, const void* ab, int B, int N, int D, const void* w_packed,
+                               const peneo_pair_dz_args* args, const void* act, void* dz, float* d_ab, float* workspace,
+                               float* partials, peneo_stream_t stream, bool e4m3) {
+  const char* const who = e4m3 ? "peneo_pair_bwd_saved_e4m3" : "peneo_pair_bwd_saved";   // the entry point the error texts name
+  PENEO_REQUIRE(args && peneo_pair_save_supported(dtype, D, args->num_heads), "%s: bf16, D = 384 only (peneo_pair_save_supported)", who);
+  PENEO_REQUIRE(ab && w_packed && act && dz && d_ab && workspace && partials && B > 0 && N > 0, "%s: bad arguments", who);
+  PENEO_REQUIRE(args->D == D && args->scale && args->num_heads * D >= 64, "%s: bad head description", who);
   PENEO_REQUIRE(((reinterpret_cast<uintptr_t>(ab) | reinterpret_cast<uintptr_t>(dz) | reinterpret_cast<uintptr_t>(act)) & 15) == 0,
-                "peneo_pair_bwd_saved: pointers must be 16-byte aligned");
+                "%s: pointers must be 16-byte aligned", who);
   for (int h = 0; h < args->num_heads; ++h)
-    PENEO_REQUIRE(args->dlogits[h] && args->w2[h] && args->classes[h] >= 1 && args->classes[h] <= 3, "peneo_pair_bwd_saved: head %d", h);
+    PENEO_REQUIRE(args->dlogits[h] && args->w2[h] && args->classes[h] >= 1 && args->classes[h] <= 3, "%s: head %d", who, h);
   PairBwdParams p;
   p.ab = reinterpret_cast<const bf16_t*>(ab); p.B = B; p.N = N; p.D = D; p.P = (int64_t)N * (N + 1) / 2;
   p.wp = w_packed; p.b1 = nullptr; p.a = *args;
   p.dz = reinterpret_cast<bf16_t*>(dz); p.x = nullptr; p.act = static_cast<const char*>(act); p.ws = workspace;
   p.ntiles = pb_num_tiles(N);
-  PENEO_REQUIRE(args->drop_p >= 0.f && args->drop_p < 1.f, "peneo_pair_bwd_saved: drop_p must be in [0, 1)");
+  PENEO_REQUIRE(args->drop_p >= 0.f && args->drop_p < 1.f, "%s: drop_p must be in [0, 1)", who);
   p.drop_thr16 = pair_drop_thr16_host(args->drop_p); p.drop_seed = args->drop_seed; p.drop_scale = pair_drop_scale_host(args->drop_p);
   p.dbg = nullptr;
   p.part_a = partials; p.part_b = partials + (size_t)B * p.ntiles * PB_TI * D;
   p.ws_own = det_mode() >= 1;
-  if (!p.ws_own) PENEO_ORDER_DEPENDENT("peneo_pair_bwd_saved");
+  if (!p.ws_own) { if (e4m3) PENEO_ORDER_DEPENDENT("peneo_pair_bwd_saved_e4m3"); else PENEO_ORDER_DEPENDENT("peneo_pair_bwd_saved"); }
   hipStream_t st = (hipStream_t)stream;
-  const int rc = p.drop_thr16 ? launch_pair_bwd_sv<24, true>(p, st) : launch_pair_bwd_sv<24, false>(p, st);
+  const int rc = e4m3 ? (p.drop_thr16 ? launch_pair_bwd_sv<24, true, true>(p, st) : launch_pair_bwd_sv<24, false, true>(p, st))
+                      : (p.drop_thr16 ? launch_pair_bwd_sv<24, true>(p, st) : launch_pair_bwd_sv<24, false>(p, st));
   if (rc != PENEO_OK) return rc;
   hipLaunchKernelGGL(pair_bwd_reduce_kernel, dim3((unsigned)N, (unsigned)B), dim3(256), 0, st, p.part_a, p.part_b, N, D, p.ntiles, d_ab);
-  return check_launch("peneo_pair_bwd_saved (reduce)");
+  return check_launch(e4m3 ? "peneo_pair_bwd_saved_e4m3 (reduce)" : "peneo_pair_bwd_saved (reduce)");
+}
+
+extern "C" int peneo_pair_bwd_saved(int dtype, const void* ab, int B, int N, int D, const void* w_packed,
+                                    const peneo_pair_dz_args* args, const void* act, void* dz, float* d_ab, float* workspace,
+                                    float* partials, peneo_stream_t stream) {
+  return pair_bwd_saved_impl(dtype, ab, B, N, D, w_packed, args, act, dz, d_ab, workspace, partials, stream, false);
+}
+
+// the same launch on the 1 KiB e4m3 records of peneo_pair_heads_fwd_save_e4m3 (common.h: PB_REC8_BYTES)
+extern "C" int peneo_pair_bwd_saved_e4m3(int dtype, const void* ab, int B, int N, int D, const void* w_packed,
+                                         const peneo_pair_dz_args* args, const void* act, void* dz, float* d_ab, float* workspace,
+                                         float* partials, peneo_stream_t stream) {
+  PENEO_REQUIRE(args && peneo_pair_save_e4m3_supported(dtype, D, args->num_heads), "peneo_pair_bwd_saved_e4m3: bf16, D = 384 only (peneo_pair_save_e4m3_supported)");
+  return pair_bwd_saved_impl(dtype, ab, B, N, D, w_packed, args, act, dz, d_ab, workspace, partials, stream, true);
 }
 
 extern "C" int peneo_pair_bwd_fused(int dtype, const void* ab, int B, int N, int D, const void* w_packed, const float* b1,

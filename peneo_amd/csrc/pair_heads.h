@@ -21,6 +21,7 @@ struct PairFwdParams {
   // saving form (hand kernel only): the pairs are walked in the backward's blocks and the kernel leaves q / y records (common.h:
   // PB_REC_BYTES) and x = SiLU(a_i + b_j) in block-row order for peneo_pair_bwd_saved; NULL = the plain walk, nothing saved
   char* act; bf16_t* x_save; int ntiles;
+  int act_e4m3;      // the records are the 1 KiB e4m3 form (common.h: PB_REC8_BYTES; peneo_pair_heads_fwd_save_e4m3)
 };
 
 constexpr float NEG_INF_F = -3.0e38f;

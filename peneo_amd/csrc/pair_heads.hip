@@ -781,8 +781,11 @@ template <int N, int I = 0, typename F> __device__ __forceinline__ void ph_stati
   if constexpr (I < N) { f(std::integral_constant<int, I>{}); ph_static_for<N, I + 1>(f); }
 }
 
-template <int KS, bool DROP, bool SAVE>
+// E4M3 (with SAVE): the records are the 1 KiB e4m3 form of common.h (PB_REC8_BYTES) instead of the 2 KiB f16 form; the walk, the
+// arithmetic and everything else the kernel writes are the same statements
+template <int KS, bool DROP, bool SAVE, bool E4M3 = false>
 __global__ __launch_bounds__(PH_WAVES * 64, 2) void pair_heads_fwd_hand_kernel(PairFwdParams p) {
+  static_assert(SAVE || !E4M3, "the e4m3 records are a form of the saving walk");
   using T = bf16_t;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int NF = KS + 2;
@@ -903,8 +906,15 @@ __global__ __launch_bounds__(PH_WAVES * 64, 2) void pair_heads_fwd_hand_kernel(P
   // records of this wave's group: slab s at + s * 4 groups * PB_REC_BYTES; the lane's 16-byte pieces at row (lane & 31), byte 16 half (+ 32)
   // (tile layout, common.h: two 1 KiB halves of 16 units each, 32-byte rows, the second half's rows XORed with 4: every store below is
   // 1 KiB contiguous, and the backward's transposing reads of the two halves fall on different banks)
-  char* const rec_l = SAVE ? p.act + ((((int64_t)b * p.ntiles + tile) * nslab * 4 + (wave & 3)) * PB_REC_BYTES + 16 * half) : nullptr;
+  constexpr int REC_BYTES = E4M3 ? PB_REC8_BYTES : PB_REC_BYTES;
+  char* const rec_l = SAVE ? p.act + ((((int64_t)b * p.ntiles + tile) * nslab * 4 + (wave & 3)) * REC_BYTES + (E4M3 ? 0 : 16 * half)) : nullptr;
   const int rec_r0 = (lane & 31) * 32, rec_r1 = 1024 + ((lane & 31) ^ 4) * 32;
+  // e4m3 records (common.h): the lane's one 16-byte piece of a slab = row pb_rec8_row(pair) of 64 bytes, piece 2 (pair & 1) + half;
+  // an even pair's lane fills it with the units of groups 0, 1 of its own pair and of its odd neighbour, the odd pair's lane with groups 2, 3
+  const int rec8_off = pb_rec8_row(lane & 31) * 64 + (2 * (lane & 1) + half) * 16;
+  const bool rec8_odd = (lane & 1) != 0;
+  // v_perm_b32 selectors (bytes 4..7: the lane's own dword, 0..3: the neighbour's) that interleave (even pair, odd pair) per unit
+  const uint32_t rec8_lo = rec8_odd ? 0x05010400u : 0x01050004u, rec8_hi = rec8_odd ? 0x07030602u : 0x03070206u;
 
   // K12 dropout.  A dropped unit's accumulator STARTS at -30000 instead of its bias: SiLU(-30000 + ...) = -0, so y needs no mask of
   // its own and the pre-activation the saving form stores is already masked (the backward's SiLU' of it is 0 as well).  The start
@@ -937,10 +947,14 @@ __global__ __launch_bounds__(PH_WAVES * 64, 2) void pair_heads_fwd_hand_kernel(P
     float t[4], u[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) { asm volatile("" : "=v"(t[e])); asm volatile("" : "=v"(u[e])); }
-    uint32_t yp[8], zp[8];
+    uint32_t yp[8], zp[8], zq[4];
 #pragma unroll
     for (int i = 0; i < 8; ++i) { asm volatile("" : "=v"(yp[i])); if constexpr (SAVE) asm volatile("" : "=v"(zp[i])); }
-    char* const rec = SAVE ? rec_l + (int64_t)(slab - 1) * (4 * PB_REC_BYTES) : nullptr;
+    if constexpr (E4M3) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) asm volatile("" : "=v"(zq[i]));
+    }
+    char* const rec = SAVE ? rec_l + (int64_t)(slab - 1) * (4 * REC_BYTES) : nullptr;
     // groups G, G + 1 done: the two halves of a pair's lanes hold 4 + 4 consecutive units of each group; a v_permlane32_swap pair makes
     // 16 contiguous bytes per lane (lanes 0-31: group G, lanes 32-63: group G + 1)
     auto save_rows = [&](auto gc) {
@@ -956,6 +970,18 @@ __global__ __launch_bounds__(PH_WAVES * 64, 2) void pair_heads_fwd_hand_kernel(P
         if constexpr ((PH_ABLATE & 4) != 0) *dst = val; else __builtin_nontemporal_store(val, dst);
       }
       if constexpr ((PH_ABLATE & 1) != 0) asm volatile("" :: "v"(zx[0]), "v"(zy[0]), "v"(zx[1]), "v"(zy[1]));
+    };
+    // e4m3 form: zq[G] holds the lane's four units of group G as bytes.  Lanes of an even and an odd pair exchange two dwords
+    // (quad_perm [1, 0, 3, 2]) and interleave them, so a lane leaves with eight units x (even pair, odd pair) = one 16-byte store per slab
+    auto save_rec8 = [&]() {
+      const uint32_t keep0 = rec8_odd ? zq[2] : zq[0], keep1 = rec8_odd ? zq[3] : zq[1];
+      const uint32_t send0 = rec8_odd ? zq[0] : zq[2], send1 = rec8_odd ? zq[1] : zq[3];
+      const uint32_t got0 = (uint32_t)__builtin_amdgcn_mov_dpp((int)send0, 0xB1, 0xF, 0xF, false);
+      const uint32_t got1 = (uint32_t)__builtin_amdgcn_mov_dpp((int)send1, 0xB1, 0xF, 0xF, false);
+      typedef unsigned int ph_u4 __attribute__((ext_vector_type(4)));
+      const ph_u4 val = ph_u4{__builtin_amdgcn_perm(keep0, got0, rec8_lo), __builtin_amdgcn_perm(keep0, got0, rec8_hi),
+                              __builtin_amdgcn_perm(keep1, got1, rec8_lo), __builtin_amdgcn_perm(keep1, got1, rec8_hi)};
+      if (tile_ok) __builtin_nontemporal_store(val, reinterpret_cast<ph_u4*>(rec + rec8_off));
     };
     // DROP: the chain run here belongs to slab + 1 (see start_values)
     constexpr bool NEXT = DROP && DOM && DOE;
@@ -978,6 +1004,9 @@ __global__ __launch_bounds__(PH_WAVES * 64, 2) void pair_heads_fwd_hand_kernel(P
       } else if constexpr (S == 1) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) u[e] = (PH_ABLATE & 8) ? u[e] : __builtin_amdgcn_exp2f(u[e]);
+        // e4m3fn(RNE(clamp(v, -448, 448))) of the f16 values v the f16 form stores: the clamp is explicit (the conversion of a larger
+        // magnitude is NaN unless the wave runs with FP16_OVFL), and it is what turns the -30000 of a dropped unit into -448
+        if constexpr (E4M3) zq[G] = pack_e4m3x4_clamped(zp[2 * G], zp[2 * G + 1]);
       } else if constexpr (S == 2) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) u[e] = u[e] + 1.f;
@@ -1001,6 +1030,7 @@ __global__ __launch_bounds__(PH_WAVES * 64, 2) void pair_heads_fwd_hand_kernel(P
       asm volatile("" : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]), "+v"(u[0]), "+v"(u[1]), "+v"(u[2]), "+v"(u[3]), "+v"(st), "+v"(sinc));
       if constexpr (S == 5) asm volatile("" : "+v"(yp[2 * G]), "+v"(yp[2 * G + 1]));
       if constexpr (S == 0 && SAVE) asm volatile("" : "+v"(zp[2 * G]), "+v"(zp[2 * G + 1]));
+      if constexpr (S == 1 && E4M3) asm volatile("" : "+v"(zq[G]));
       if constexpr (S >= 4 && NEXT) asm volatile("" : "+v"(zr));
       // groups 0, 1 done: y rows 0..15 of the slab are complete -> the first second-layer MFMA
       if constexpr (Q == 11) ph_mma_late(w2a, ph_u32x4{yp[0], yp[1], yp[2], yp[3]}, lg);
@@ -1008,8 +1038,9 @@ __global__ __launch_bounds__(PH_WAVES * 64, 2) void pair_heads_fwd_hand_kernel(P
         if constexpr (DOM) ph_mma_late(w2b, ph_u32x4{yp[4], yp[5], yp[6], yp[7]}, lg);
         else ph_mma_late_final(w2b, ph_u32x4{yp[4], yp[5], yp[6], yp[7]}, lg);
       }
-      if constexpr (SAVE && Q == 11) save_rows(std::integral_constant<int, 0>{});
-      if constexpr (SAVE && Q == 23) save_rows(std::integral_constant<int, 2>{});
+      if constexpr (SAVE && !E4M3 && Q == 11) save_rows(std::integral_constant<int, 0>{});
+      if constexpr (SAVE && !E4M3 && Q == 23) save_rows(std::integral_constant<int, 2>{});
+      if constexpr (E4M3 && Q == 23) save_rec8();
     };
     if constexpr (DOM) {
       ph_static_for<KS>([&](auto kc) {
@@ -1099,19 +1130,20 @@ __global__ __launch_bounds__(PH_WAVES * 64, 2) void pair_heads_fwd_hand_kernel(P
   pair_epilogue(p, lg, smem, tid, lane, wave, half, b, mypair, pair_ok);
 }
 
-template <int KS, bool DROP, bool SAVE>
+template <int KS, bool DROP, bool SAVE, bool E4M3 = false>
 static int launch_pair_fwd_hand(const PairFwdParams& p, hipStream_t st) {
+  constexpr const char* who = E4M3 ? "peneo_pair_heads_fwd_save_e4m3" : "peneo_pair_heads_fwd";
   const size_t slab = (size_t)slab_stride_bytes(KS * 16, 2);
   const size_t nstage = 4 * slab + 5 * 512 * 4 <= 160 * 1024 ? 4 : 3;      // as in the kernel
   size_t sh = nstage * slab + (size_t)p.num_heads * p.D * sizeof(float);
-  if (sh > 160 * 1024) { set_error("peneo_pair_heads_fwd: D=%d needs %zu bytes of LDS", p.D, sh); return PENEO_ERR_INVALID; }
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(pair_heads_fwd_hand_kernel<KS, DROP, SAVE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh) != hipSuccess) {
-    set_error("peneo_pair_heads_fwd: cannot raise dynamic LDS to %zu bytes", sh);
+  if (sh > 160 * 1024) { set_error("%s: D=%d needs %zu bytes of LDS", who, p.D, sh); return PENEO_ERR_INVALID; }
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(pair_heads_fwd_hand_kernel<KS, DROP, SAVE, E4M3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh) != hipSuccess) {
+    set_error("%s: cannot raise dynamic LDS to %zu bytes", who, sh);
     return PENEO_ERR_LAUNCH;
   }
   dim3 grid(SAVE ? (unsigned)((p.ntiles + 1) / 2) : (unsigned)((p.P + PH_PAIRS - 1) / PH_PAIRS), p.B);
-  hipLaunchKernelGGL((pair_heads_fwd_hand_kernel<KS, DROP, SAVE>), grid, dim3(PH_WAVES * 64), sh, st, p);
-  return check_launch("peneo_pair_heads_fwd");
+  hipLaunchKernelGGL((pair_heads_fwd_hand_kernel<KS, DROP, SAVE, E4M3>), grid, dim3(PH_WAVES * 64), sh, st, p);
+  return check_launch(who);
 }
 
 template <typename T, int KS, int VARIANT, bool DROP>
@@ -1141,6 +1173,10 @@ template <typename T, int KS>
 static int launch_pair_fwd(const PairFwdParams& p, hipStream_t st) {
   constexpr int V = sizeof(T) == 2 ? PH_DEFAULT_VARIANT : 0;
   if constexpr (sizeof(T) == 2 && (KS == 24 || KS == 32)) {
+    if constexpr (KS == 24) {
+      if (p.act && p.act_e4m3 && p.num_heads * p.D / 32 >= 2)
+        return p.drop_thr16 ? launch_pair_fwd_hand<KS, true, true, true>(p, st) : launch_pair_fwd_hand<KS, false, true, true>(p, st);
+    }
     if (p.act && KS == 24 && p.num_heads * p.D / 32 >= 2)
       return p.drop_thr16 ? launch_pair_fwd_hand<KS, true, true>(p, st) : launch_pair_fwd_hand<KS, false, true>(p, st);
     if (pair_fwd_hand() && p.num_heads * p.D / 32 >= 2)
@@ -1545,24 +1581,28 @@ extern "C" int peneo_pair_heads_pack(int dtype, const float* const* w1, const fl
 }
 
 static int pair_heads_fwd_impl(int dtype, const void* ab, int B, int N, const peneo_pair_heads_desc* desc,
-                               float* const* logits, const peneo_pair_loss* loss, void* act, void* x_rows, peneo_stream_t stream) {
-  PENEO_REQUIRE(ok_dt(dtype) && ab && desc && B > 0 && N > 0, "peneo_pair_heads_fwd: bad arguments");
-  PENEO_REQUIRE(desc->num_heads > 0 && desc->num_heads <= PENEO_MAX_HEADS, "peneo_pair_heads_fwd: num_heads out of range");
-  PENEO_REQUIRE(desc->D > 0 && desc->D % 32 == 0, "peneo_pair_heads_fwd: D must be a multiple of 32");
-  PENEO_REQUIRE(desc->w_packed && desc->b1 && desc->b2, "peneo_pair_heads_fwd: null weights");
+                               float* const* logits, const peneo_pair_loss* loss, void* act, void* x_rows, peneo_stream_t stream,
+                               bool act_e4m3 = false) {
+  // the entry point the error texts name (the f16 saving form has always reported as peneo_pair_heads_fwd / _save)
+  const char* const who = act_e4m3 ? "peneo_pair_heads_fwd_save_e4m3" : "peneo_pair_heads_fwd";
+  const char* const who_save = act_e4m3 ? "peneo_pair_heads_fwd_save_e4m3" : "peneo_pair_heads_fwd_save";
+  PENEO_REQUIRE(ok_dt(dtype) && ab && desc && B > 0 && N > 0, "%s: bad arguments", who);
+  PENEO_REQUIRE(desc->num_heads > 0 && desc->num_heads <= PENEO_MAX_HEADS, "%s: num_heads out of range", who);
+  PENEO_REQUIRE(desc->D > 0 && desc->D % 32 == 0, "%s: D must be a multiple of 32", who);
+  PENEO_REQUIRE(desc->w_packed && desc->b1 && desc->b2, "%s: null weights", who);
   PENEO_REQUIRE((reinterpret_cast<uintptr_t>(desc->w_packed) & 15) == 0 && (reinterpret_cast<uintptr_t>(ab) & 15) == 0,
-                "peneo_pair_heads_fwd: ab / packed weights must be 16-byte aligned");
+                "%s: ab / packed weights must be 16-byte aligned", who);
   PairFwdParams p = {};
   p.ab = ab; p.B = B; p.N = N; p.D = desc->D; p.P = (int64_t)N * (N + 1) / 2; p.num_heads = desc->num_heads;
   p.total_classes = total_classes(desc->classes, desc->num_heads);
-  PENEO_REQUIRE(p.total_classes <= NCP, "peneo_pair_heads_fwd: more than %d classes in total", NCP);
+  PENEO_REQUIRE(p.total_classes <= NCP, "%s: more than %d classes in total", who, NCP);
   p.wp = desc->w_packed; p.b1 = desc->b1; p.b2 = desc->b2;
-  PENEO_REQUIRE(desc->drop_p >= 0.f && desc->drop_p < 1.f, "peneo_pair_heads_fwd: drop_p must be in [0, 1)");
-  PENEO_REQUIRE((int64_t)p.P * (desc->num_heads * desc->D / 16) < ((int64_t)1 << 32), "peneo_pair_heads_fwd: pair space too large for the dropout counter");
+  PENEO_REQUIRE(desc->drop_p >= 0.f && desc->drop_p < 1.f, "%s: drop_p must be in [0, 1)", who);
+  PENEO_REQUIRE((int64_t)p.P * (desc->num_heads * desc->D / 16) < ((int64_t)1 << 32), "%s: pair space too large for the dropout counter", who);
   p.drop_thr16 = pair_drop_thr16_host(desc->drop_p); p.drop_seed = desc->drop_seed;
   p.drop_scale = p.drop_thr16 ? 65536.f / (65536.f - (float)p.drop_thr16) : 1.f;
   for (int h = 0; h < desc->num_heads; ++h) {
-    PENEO_REQUIRE(desc->classes[h] >= 1 && desc->classes[h] <= 4, "peneo_pair_heads_fwd: classes[%d] must be 1..4", h);
+    PENEO_REQUIRE(desc->classes[h] >= 1 && desc->classes[h] <= 4, "%s: classes[%d] must be 1..4", who, h);
     p.classes[h] = desc->classes[h];
     p.logits[h] = logits ? logits[h] : nullptr;
     if (loss) { p.tags[h] = loss->tags[h]; p.cw[h] = loss->class_weight[h]; p.dlogits[h] = loss->dlogits[h]; }
@@ -1571,12 +1611,13 @@ static int pair_heads_fwd_impl(int dtype, const void* ab, int B, int N, const pe
     p.partials = loss->partials;
     bool any = false;
     for (int h = 0; h < desc->num_heads; ++h) any = any || loss->tags[h];
-    if (any) PENEO_REQUIRE(p.partials, "peneo_pair_heads_fwd: loss->partials workspace missing");
+    if (any) PENEO_REQUIRE(p.partials, "%s: loss->partials workspace missing", who);
   }
   if (act) {
-    PENEO_REQUIRE(x_rows && peneo_pair_save_supported(dtype, desc->D, desc->num_heads), "peneo_pair_heads_fwd_save: not supported for this dtype / D (peneo_pair_save_supported)");
-    PENEO_REQUIRE((reinterpret_cast<uintptr_t>(act) & 15) == 0 && (reinterpret_cast<uintptr_t>(x_rows) & 15) == 0, "peneo_pair_heads_fwd_save: act / x must be 16-byte aligned");
+    PENEO_REQUIRE(x_rows && peneo_pair_save_supported(dtype, desc->D, desc->num_heads), "%s: not supported for this dtype / D (peneo_pair_save_supported)", who_save);
+    PENEO_REQUIRE((reinterpret_cast<uintptr_t>(act) & 15) == 0 && (reinterpret_cast<uintptr_t>(x_rows) & 15) == 0, "%s: act / x must be 16-byte aligned", who_save);
     p.act = static_cast<char*>(act); p.x_save = static_cast<bf16_t*>(x_rows); p.ntiles = pb_num_tiles(N);
+    p.act_e4m3 = act_e4m3 ? 1 : 0;
   }
   return dtype == PENEO_BF16 ? dispatch_pair_fwd<bf16_t>(p, (hipStream_t)stream) : dispatch_pair_fwd<float>(p, (hipStream_t)stream);
 }
@@ -1598,6 +1639,17 @@ extern "C" int peneo_pair_heads_fwd_save(int dtype, const void* ab, int B, int N
                                          peneo_stream_t stream) {
   PENEO_REQUIRE(act && x_rows, "peneo_pair_heads_fwd_save: null act / x");
   return pair_heads_fwd_impl(dtype, ab, B, N, desc, logits, loss, act, x_rows, stream);
+}
+
+extern "C" int peneo_pair_save_e4m3_supported(int dtype, int D, int num_heads) { return peneo_pair_save_supported(dtype, D, num_heads); }
+extern "C" size_t peneo_pair_save_e4m3_bytes(int B, int N, int num_heads, int D) {
+  return B > 0 && N > 0 && num_heads > 0 && D > 0 ? (size_t)B * pb_num_tiles(N) * (num_heads * D / 32) * 4 * PB_REC8_BYTES : 0;
+}
+extern "C" int peneo_pair_heads_fwd_save_e4m3(int dtype, const void* ab, int B, int N, const peneo_pair_heads_desc* desc,
+                                              float* const* logits, const peneo_pair_loss* loss, void* act, void* x_rows,
+                                              peneo_stream_t stream) {
+  PENEO_REQUIRE(act && x_rows, "peneo_pair_heads_fwd_save_e4m3: null act / x");
+  return pair_heads_fwd_impl(dtype, ab, B, N, desc, logits, loss, act, x_rows, stream, true);
 }
 
 static int chunk_check(const char* who, int dtype, int N, int D, int i0, int i1) {

@@ -175,6 +175,9 @@ SIGNATURES = {
     "peneo_pair_save_bytes": (_sz, [_i, _i, _i, _i]),
     "peneo_pair_loss_partials_save": (_i64, [_i, _i]),
     "peneo_pair_heads_fwd_save": (_i, [_i, _vp, _i, _i, C.POINTER(PairHeadsDesc), _vp, C.POINTER(PairLoss), _vp, _vp, _vp]),
+    "peneo_pair_save_e4m3_supported": (_i, [_i, _i, _i]),
+    "peneo_pair_save_e4m3_bytes": (_sz, [_i, _i, _i, _i]),
+    "peneo_pair_heads_fwd_save_e4m3": (_i, [_i, _vp, _i, _i, C.POINTER(PairHeadsDesc), _vp, C.POINTER(PairLoss), _vp, _vp, _vp]),
     "peneo_mxfp8_quantize_rows": (_i, [_vp, _i64, _i64, _vp, _vp, _vp]),
     "peneo_mxfp8_quantize_rows_bf16": (_i, [_vp, _i64, _i64, _i64, _vp, _vp, _vp]),
     "peneo_layernorm_mxfp8_supported": (_i, [_i]),
@@ -188,6 +191,7 @@ SIGNATURES = {
     "peneo_pair_mxfp8_save_supported": (_i, [_i, _i]),
     "peneo_pair_heads_fwd_mxfp8_save": (_i, [_vp, _i, _i, C.POINTER(PairHeadsDesc), _vp, C.POINTER(PairLoss), _vp, _vp, _vp]),
     "peneo_pair_bwd_saved": (_i, [_i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "peneo_pair_bwd_saved_e4m3": (_i, [_i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "peneo_ohem_workspace_bytes": (_sz, [_i64]),
     "peneo_ohem_ce": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "peneo_ohem_finish": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp]),

@@ -275,12 +275,16 @@ class _DecoderStage(torch.autograd.Function):
         # hidden unit (4.2 GB at 8 x 511 tokens) - the backward then neither repeats the first-layer product nor the dropout chain
         save = (need_grad and tags is not None and dec.fused_bwd and dec.save_pair_act and ops.pair_bwd_supported(dt, D, len(HEAD_NAMES))
                 and ops.pair_save_supported(dt, D, len(HEAD_NAMES)))
+        # opt-in e4m3 records (set_pair_act_format): one byte per pair and hidden unit, half the buffer and half the stream
+        # (pair_save_e4m3_supported is pair_save_supported: whatever saves at all can save in either format)
+        act_e4m3 = save and dec.pair_act_format == "e4m3"
         bufs = None
         if save:
             # (step-sized buffers are kept between steps: engine.big_acquire.)  The saved form is an optimisation that costs memory:
             # when its buffers do not fit, the step continues on the recomputing backward, which needs none of them
             try:
-                act, act_h = big_acquire("pair_act", (ops.pair_save_bytes(B, N, len(HEAD_NAMES), D),), torch.uint8, dev)
+                act_bytes = (ops.pair_save_e4m3_bytes if act_e4m3 else ops.pair_save_bytes)(B, N, len(HEAD_NAMES), D)
+                act, act_h = big_acquire("pair_act", (act_bytes,), torch.uint8, dev)
                 try:
                     xr, xr_h = big_acquire("pair_x", (B * ops.pair_bwd_rows(N), D), dt, dev)
                 except torch.cuda.OutOfMemoryError:
@@ -288,6 +292,7 @@ class _DecoderStage(torch.autograd.Function):
                     raise
                 bufs = (act, xr)
                 saved["pair_act"], saved["pair_x"] = (act, act_h), (xr, xr_h)
+                saved["pair_act_format"] = "e4m3" if act_e4m3 else "f16"
             except torch.cuda.OutOfMemoryError:
                 big_clear(dev)
                 save = False
@@ -304,7 +309,8 @@ class _DecoderStage(torch.autograd.Function):
                                                                              [w.detach() for w in w2s]))
         res = ops.pair_heads_fwd(ab, wp, b1cat, b2cat, HEAD_CLASSES, want_logits=want_logits,
                                  tags=tags, class_weights=cws, want_dlogits=need_grad and tags is not None,
-                                 drop_p=seeds.p_hidden, drop_seed=seeds.seed(903), save=save, save_buffers=bufs)
+                                 drop_p=seeds.p_hidden, drop_seed=seeds.seed(903), save=save, save_buffers=bufs,
+                                 save_format="e4m3" if save and act_e4m3 else "f16")
         return _DecoderStage._finish(ctx, dec, saved, params, res, tags, cws, ab, B, N, D, seq, dev)
 
     @staticmethod
@@ -403,7 +409,7 @@ class _DecoderStage(torch.autograd.Function):
             if "pair_act" in sv:
                 xbuf1, x_h = sv.pop("pair_x")
                 act, act_h = sv.pop("pair_act")
-                ops.pair_bwd_saved(ab, wp2, dza, act, dzbuf, d_ab, dz_ws)
+                ops.pair_bwd_saved(ab, wp2, dza, act, dzbuf, d_ab, dz_ws, act_format=sv["pair_act_format"])   # (what the forward wrote)
                 big_release("pair_act", act_h)           # (read by that launch only: the next forward's stores are ordered behind it)
             else:
                 xbuf1, x_h = big_acquire("pair_x", (B * rows, D), dt, dev)
@@ -709,6 +715,7 @@ class PEneoDecoder(nn.Module):
         self.decoder_hidden_size = D
         self.pair_heads_format = "bf16"   # set_pair_heads_format
         self.pair_heads_train_format = "bf16"   # set_pair_heads_train_format
+        self.pair_act_format = "f16"            # set_pair_act_format
         self.handshaking_kernel = HandshakingKernel(D)
         self.inference_mode = config.inference_mode
 
@@ -787,7 +794,34 @@ class PEneoDecoder(nn.Module):
                 raise ValueError(f"the mxfp8 train format of the pair heads does not support decoder width D = {self.decoder_hidden_size}")
             if not (self.save_pair_act and self.fused_bwd):
                 raise ValueError("the mxfp8 train format of the pair heads feeds the saved backward: save_pair_act and fused_bwd must be on")
+            if self.pair_act_format == "e4m3":
+                raise ValueError("the mxfp8 train forward writes f16 records: switch back with set_pair_act_format('f16') first")
         self.pair_heads_train_format = fmt
+
+    def set_pair_act_format(self, fmt: str, compute_dtype: torch.dtype = torch.bfloat16) -> None:
+        """"f16" (default): a train step that saves the classifiers' pre-activations for the fused backward (save_pair_act) keeps them
+        as f16, 2 bytes per pair and hidden unit.  "e4m3": as e4m3fn bytes (peneo_pair_heads_fwd_save_e4m3 / peneo_pair_bwd_saved_e4m3;
+        include/peneo_hip.h): half the buffer and half the bytes streamed; the forward's losses are unchanged, the backward takes
+        SiLU and SiLU' at z rounded to 3 mantissa bits (|z| above 448 saturates).  Needs bf16 compute, the 2-layer classifiers, a width
+        the e4m3 form holds (384) and the saved backward switched on (save_pair_act / fused_bwd); not together with
+        set_pair_heads_train_format("mxfp8"), whose kernel writes f16 records.
+        Memory: the step-sized buffers are kept between steps and a kept buffer that is large enough is handed out again
+        (engine.big_acquire), so a process that has already trained with "f16" keeps its full-sized buffer after the switch; the saving
+        shows once the kept buffers are dropped (train(False) or engine.big_clear()) or in a process that starts with "e4m3"."""
+        if fmt not in ops.PAIR_ACT_FORMATS:
+            raise ValueError(f"unknown pair activation format {fmt!r} (expected 'f16' or 'e4m3')")
+        if fmt == "e4m3":
+            if compute_dtype != torch.bfloat16:
+                raise ValueError("the e4m3 pair activations need compute dtype torch.bfloat16")
+            if self.num_cls_layers != 2:
+                raise ValueError(f"the e4m3 pair activations need peneo_classifier_num_layers == 2, not {self.num_cls_layers}")
+            if not ops.pair_save_e4m3_supported(torch.bfloat16, self.decoder_hidden_size, len(HEAD_NAMES)):
+                raise ValueError(f"the e4m3 pair activations do not support decoder width D = {self.decoder_hidden_size}")
+            if not (self.save_pair_act and self.fused_bwd):
+                raise ValueError("the e4m3 pair activations are those of the saved backward: save_pair_act and fused_bwd must be on")
+            if self.pair_heads_train_format == "mxfp8":
+                raise ValueError("the mxfp8 train forward writes f16 records: switch back with set_pair_heads_train_format('bf16') first")
+        self.pair_act_format = fmt
 
     def fused_pair_heads(self, dt: torch.dtype, D: int) -> bool:
         """True where the forward runs the fused pair-heads kernel: the 2-layer classifiers at a (dtype, width) the library has one
@@ -870,6 +904,14 @@ class PEneoDecoder(nn.Module):
                 raise ValueError("the mxfp8 train format of the pair heads needs compute dtype torch.bfloat16")
             if not (self.save_pair_act and self.fused_bwd):
                 raise ValueError("the mxfp8 train format of the pair heads feeds the saved backward: save_pair_act and fused_bwd must be on")
+        if self.pair_act_format == "e4m3" and need_grad:
+            # what set_pair_act_format checked may have been changed since
+            if sequence_output.dtype != torch.bfloat16:
+                raise ValueError("the e4m3 pair activations need compute dtype torch.bfloat16")
+            if not (self.save_pair_act and self.fused_bwd):
+                raise ValueError("the e4m3 pair activations are those of the saved backward: save_pair_act and fused_bwd must be on")
+            if self.pair_heads_train_format == "mxfp8":
+                raise ValueError("the mxfp8 train forward writes f16 records: it cannot run with the e4m3 pair activations")
         res = _DecoderStage.apply(self, sequence_output.reshape(B * N, Hin), B, N, tags, want_logits, need_grad, *params)
         loss, l_le, l_elh, l_elt, l_lgh, l_lgt, o_le, o_elh, o_elt, o_lgh, o_lgt = res
         if self.inference_mode:

@@ -821,11 +821,15 @@ def pair_heads_pack(dtype: torch.dtype, w1: Sequence[torch.Tensor], w2: Sequence
 def pair_heads_fwd(ab: torch.Tensor, wp: torch.Tensor, b1: torch.Tensor, b2: torch.Tensor,
                    classes: Sequence[int], *, want_logits: bool = True, tags: Optional[Sequence[torch.Tensor]] = None,
                    class_weights: Optional[Sequence[Optional[torch.Tensor]]] = None, want_dlogits: bool = False,
-                   drop_p: float = 0.0, drop_seed: int = 0, save: bool = False, save_buffers=None):
+                   drop_p: float = 0.0, drop_seed: int = 0, save: bool = False, save_buffers=None, save_format: str = "f16"):
     """ab: [B, N, 2D].  Returns (logits list | None, loss partials [n, 32] | None, dlogits list | None).
     drop_p / drop_seed: the Dropout between the two classifier layers (train mode, model/peneo_decoder.py:261).
     save (pair_save_supported): the launch also leaves the hidden activations the backward needs; returns a fourth value
-    (act [bytes] uint8, x_rows [B * pair_bwd_rows(N), D]) for pair_bwd_saved; save_buffers = (act, x_rows) supplies them."""
+    (act [bytes] uint8, x_rows [B * pair_bwd_rows(N), D]) for pair_bwd_saved; save_buffers = (act, x_rows) supplies them.
+    save_format: "f16" (2 KiB records, pair_save_bytes) or "e4m3" (1 KiB records of e4m3fn bytes, pair_save_e4m3_bytes; the backward
+    is then pair_bwd_saved(act_format="e4m3"))."""
+    if save_format not in PAIR_ACT_FORMATS:
+        raise ValueError(f"save_format must be one of {PAIR_ACT_FORMATS}, got {save_format!r}")
     _c(ab)
     B, N, D2 = ab.shape
     D = D2 // 2
@@ -856,22 +860,37 @@ def pair_heads_fwd(ab: torch.Tensor, wp: torch.Tensor, b1: torch.Tensor, b2: tor
                 loss.dlogits[h] = ptr(dlog[h])
         loss.partials = ptr(partials)
     if save:
+        e4m3 = save_format == "e4m3"
+        nbytes = lib().peneo_pair_save_e4m3_bytes(B, N, nh, D) if e4m3 else lib().peneo_pair_save_bytes(B, N, nh, D)
         if save_buffers is not None:
             act, x_rows = save_buffers
-            assert act.dtype == torch.uint8 and act.numel() >= lib().peneo_pair_save_bytes(B, N, nh, D) and act.is_contiguous()
+            assert act.dtype == torch.uint8 and act.numel() >= nbytes and act.is_contiguous()
             assert x_rows.shape == (B * pair_bwd_rows(N), D) and x_rows.dtype == ab.dtype and x_rows.is_contiguous()
         else:
-            act = torch.empty(lib().peneo_pair_save_bytes(B, N, nh, D), dtype=torch.uint8, device=ab.device)
+            act = torch.empty(nbytes, dtype=torch.uint8, device=ab.device)
             x_rows = torch.empty((B * pair_bwd_rows(N), D), dtype=ab.dtype, device=ab.device)
+        entry = "peneo_pair_heads_fwd_save_e4m3" if e4m3 else "peneo_pair_heads_fwd_save"
         with kernel_timer("pair_heads_fwd"):
-            check(lib().peneo_pair_heads_fwd_save(dtype_code(ab.dtype), ptr(ab), B, N, C.byref(desc), lp,
-                                                  C.byref(loss) if loss is not None else None, ptr(act), ptr(x_rows), stream()),
-                  "peneo_pair_heads_fwd_save")
+            check(getattr(lib(), entry)(dtype_code(ab.dtype), ptr(ab), B, N, C.byref(desc), lp,
+                                        C.byref(loss) if loss is not None else None, ptr(act), ptr(x_rows), stream()), entry)
         return logits, partials, dlog, (act, x_rows)
     with kernel_timer("pair_heads_fwd"):
         check(lib().peneo_pair_heads_fwd(dtype_code(ab.dtype), ptr(ab), B, N, C.byref(desc), lp,
                                          C.byref(loss) if loss is not None else None, stream()), "peneo_pair_heads_fwd")
     return logits, partials, dlog
+
+
+PAIR_ACT_FORMATS = ("f16", "e4m3")      # record formats of the saved pair activations (include/peneo_hip.h)
+
+
+def pair_save_e4m3_bytes(B: int, N: int, num_heads: int, D: int) -> int:
+    """Bytes of the e4m3 records of pair_heads_fwd(save=True, save_format="e4m3"): half of pair_save_bytes."""
+    return int(lib().peneo_pair_save_e4m3_bytes(int(B), int(N), int(num_heads), int(D)))
+
+
+def pair_save_e4m3_supported(dtype, D: int, num_heads: int) -> bool:
+    """True when peneo_pair_heads_fwd_save_e4m3 / peneo_pair_bwd_saved_e4m3 exist for this shape (where pair_save_supported is)."""
+    return bool(lib().peneo_pair_save_e4m3_supported(dtype_code(dtype), int(D), int(num_heads)))
 
 
 def pair_save_bytes(B: int, N: int, num_heads: int, D: int) -> int:
@@ -1221,18 +1240,20 @@ def pair_bwd_fused(ab: torch.Tensor, wp: torch.Tensor, b1: torch.Tensor, args: "
 
 
 def pair_bwd_saved(ab: torch.Tensor, wp: torch.Tensor, args: "hip.PairDzArgs", act: torch.Tensor, dz: torch.Tensor,
-                   d_ab: torch.Tensor, workspace: torch.Tensor) -> None:
+                   d_ab: torch.Tensor, workspace: torch.Tensor, act_format: str = "f16") -> None:
     """pair_bwd_fused for a forward that saved its hidden activations (pair_heads_fwd(save=True)): same outputs except x, which
-    the forward already wrote."""
+    the forward already wrote.  act_format: the save_format the forward ran with."""
+    if act_format not in PAIR_ACT_FORMATS:
+        raise ValueError(f"act_format must be one of {PAIR_ACT_FORMATS}, got {act_format!r}")
+    entry = "peneo_pair_bwd_saved_e4m3" if act_format == "e4m3" else "peneo_pair_bwd_saved"
     B, N, D2 = ab.shape
     assert d_ab.dtype == torch.float32 and d_ab.shape == ab.shape and dz.dtype == torch.bfloat16
     assert dz.shape[0] == B * pair_bwd_rows(N)
     _check_pair_bwd_workspace(workspace, B, N, args.num_heads * args.D)
     partials = torch.empty(lib().peneo_pair_bwd_partial_bytes(B, N, D2 // 2) // 4, dtype=torch.float32, device=ab.device)
     with kernel_timer("pair_bwd_saved"):
-        check(lib().peneo_pair_bwd_saved(dtype_code(ab.dtype), ptr(_c(ab)), B, N, D2 // 2, ptr(wp), C.byref(args), ptr(act),
-                                         ptr(_c(dz)), ptr(_c(d_ab)), ptr(workspace), ptr(partials), stream()),
-              "peneo_pair_bwd_saved")
+        check(getattr(lib(), entry)(dtype_code(ab.dtype), ptr(_c(ab)), B, N, D2 // 2, ptr(wp), C.byref(args), ptr(act),
+                                    ptr(_c(dz)), ptr(_c(d_ab)), ptr(workspace), ptr(partials), stream()), entry)
 
 
 def pair_dz_finish(workspace: torch.Tensor, nh: int, D: int, classes: Sequence[int]):
