@@ -587,11 +587,17 @@ int peneo_pair_dz(int dtype, void* z_inout, int64_t npairs, const peneo_pair_dz_
  * fragment-packed weight buffer of peneo_pair_heads_pack (its second-layer fragments are not used here).
  * With x_out / pre_out it also leaves x = SiLU(a_i + b_j) and a_i + b_j for the dW1 / dx GEMMs (no peneo_pair_x_fwd pass).
  * Replaces peneo_pair_x_fwd + the first-layer GEMM + peneo_pair_dz of the chunked backward
- * (the autograd graph through model/peneo_decoder.py:269-336). */
+ * (the autograd graph through model/peneo_decoder.py:269-336).
+ * Widths: D / 16 in {2, 4, 6, 8, 12, 16, 24, 32} (eight waves, 256 pairs a workgroup), and since version 110 512 < D <= 1024 with
+ * D % 64 == 0 (four waves, one per SIMD, the same 256 pairs in two rounds of 128; the packed image of peneo_pair_heads_pack for these
+ * widths; same arguments, same checks, same workspace rows).  peneo_pair_dz_fused_supported says where a kernel exists. */
 int peneo_pair_dz_fused(int dtype, const void* ab_doc, int N, int D, int i0, int i1, const void* w_packed, const float* b1,
                         const peneo_pair_dz_args* args, void* dz, float* workspace,
                         void* x_out /* optional [npairs, D]: what peneo_pair_x_fwd would write */,
                         void* pre_out /* given together with x_out */, peneo_stream_t stream);
+/* 1 exactly where peneo_pair_dz_fused has a kernel (version 110; host only, no GPU call): bf16 with the widths above, 1..8 heads,
+ * LDS permitting; 0 for everything else (fp32, other widths, no heads). */
+int peneo_pair_dz_fused_supported(int dtype, int D, int num_heads);
 
 /* Decoder backward through the pair space in ONE kernel (bf16; D / 16 in {2, 4, 8, 24, 32}): for all pairs (i, j), i <= j, of
  * all B documents it rebuilds x = SiLU(a_i + b_j) in registers, computes z = x W1cat^T + b1 and dz (as peneo_pair_dz_fused),
@@ -882,8 +888,10 @@ uint64_t peneo_order_dependent_launches(void);
 int64_t peneo_pair_bwd_workspace_rows(int B, int N);
 /* The same for peneo_pair_dz_fused (the chunked decoder backward, widths without the fused kernel): rows of its workspace for
  * launches of up to `npairs` pairs.  Mode 0: 256.  Modes 1 / 2: one row per workgroup of a launch (npairs / 256, at least 256); the
- * launches of a backward add into the rows one after the other on one stream.  peneo_pair_x_bwd runs one workgroup per row /
- * column of the triangle under the mode (no workspace). */
+ * launches of a backward add into the rows one after the other on one stream.  The four-wave kernel of the widths above 512 walks
+ * a workgroup's 256 pairs in two rounds and adds twice to each address of its row: both adds come from the same lane of the same
+ * wave, in program order, so the row still has a single writer in a fixed order and the call is not counted as order-dependent
+ * under modes 1 / 2 either.  peneo_pair_x_bwd runs one workgroup per row / column of the triangle under the mode (no workspace). */
 int64_t peneo_pair_dz_fused_workspace_rows(int64_t npairs);
 /* peneo_relpos_bias_bwd_layers / peneo_relpos_bias_bwd with the deterministic fold: under modes 1 / 2 the per-workgroup bin sums go
  * to 64-bit fixed-point accumulators in `workspace` (2^-32 units, |sum of a bin over the launch| < 2^31) with integer atomics, and

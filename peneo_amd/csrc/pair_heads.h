@@ -138,4 +138,18 @@ __host__ __device__ inline int64_t pair_wide_slab_bytes(int D) { return (int64_t
 bool pair_wide_supported(int dtype, int D, int num_heads);
 int pair_wide_fwd(const PairFwdParams& p, hipStream_t st);
 
+// peneo_pair_dz_fused: the launch parameters of pair_dz_fused_kernel (pair_heads.hip: D <= 512, eight waves) and of
+// pair_dz_wide_kernel (pair_dz_wide.hip: 512 < D <= 1024, four waves, the packed image and slab stride of the wide forward).
+struct DzFusedParams {
+  const bf16_t* abd; int N, D; int64_t pbase, npairs;
+  const void* wp; const float* b1;
+  peneo_pair_dz_args a;
+  bf16_t* out; float* ws;
+  bf16_t* x_out; bf16_t* pre_out;   // optional [npairs, D]: SiLU(a_i + b_j) and a_i + b_j for the dW1 / dx GEMMs
+  int ws_own;                       // deterministic mode: workspace row = workgroup (one add per address and launch), else % DZF_SLOTS
+};
+constexpr int DZF_SLOTS = 256;
+bool pair_dz_wide_supported(int dtype, int D, int num_heads);
+int pair_dz_wide(const DzFusedParams& p, hipStream_t st);
+
 }  // namespace peneo

@@ -1219,15 +1219,7 @@ static int dispatch_pair_fwd(const PairFwdParams& p, hipStream_t st) {
 #ifndef DZF_ABLATE
 #define DZF_ABLATE 0   // timing experiments only (tools/): 1 no stores, 2 no dz arithmetic, 4 no g reads, 8 no exp/rcp, 16 no MFMA
 #endif
-struct DzFusedParams {
-  const bf16_t* abd; int N, D; int64_t pbase, npairs;
-  const void* wp; const float* b1;
-  peneo_pair_dz_args a;
-  bf16_t* out; float* ws;
-  bf16_t* x_out; bf16_t* pre_out;   // optional [npairs, D]: SiLU(a_i + b_j) and a_i + b_j for the dW1 / dx GEMMs
-  int ws_own;                       // deterministic mode: workspace row = workgroup (one add per address and launch), else % DZF_SLOTS
-};
-constexpr int DZF_SLOTS = 256;
+// (DzFusedParams, DZF_SLOTS: pair_heads.h, shared with the four-wave kernel of pair_dz_wide.hip)
 
 template <int KS, bool PIPE>
 __global__ __launch_bounds__(PH_WAVES * 64, 2) void pair_dz_fused_kernel(DzFusedParams p) {
@@ -1729,7 +1721,8 @@ extern "C" int peneo_pair_dz_fused(int dtype, const void* ab_doc, int N, int D, 
   PENEO_REQUIRE(args->drop_p >= 0.f && args->drop_p < 1.f, "peneo_pair_dz_fused: drop_p must be in [0, 1)");
   DzFusedParams p;
   // deterministic mode: a workspace row per workgroup of the launch (peneo_pair_dz_fused_workspace_rows), so every address receives
-  // one add per launch, and the launches of a backward follow each other on one stream
+  // one add per launch, and the launches of a backward follow each other on one stream (the four-wave kernel of D > 512: two adds, by
+  // the same lane in program order - a single writer in a fixed order, so it is not counted either)
   p.ws_own = det_mode() >= 1;
   if (!p.ws_own) PENEO_ORDER_DEPENDENT("peneo_pair_dz_fused");   // workgroups share the workspace rows (fp32 atomics)
   p.abd = reinterpret_cast<const bf16_t*>(ab_doc); p.N = N; p.D = D;
@@ -1737,6 +1730,7 @@ extern "C" int peneo_pair_dz_fused(int dtype, const void* ab_doc, int N, int D, 
   p.wp = w_packed; p.b1 = b1; p.a = *args; p.out = reinterpret_cast<bf16_t*>(dz); p.ws = workspace;
   p.x_out = reinterpret_cast<bf16_t*>(x_out); p.pre_out = reinterpret_cast<bf16_t*>(pre_out);
   hipStream_t st = (hipStream_t)stream;
+  if (pair_dz_wide_supported(dtype, D, args->num_heads)) return pair_dz_wide(p, st);   // 512 < D <= 1024: pair_dz_wide.hip
   switch (D / 16) {
     case 2: return launch_pair_dz_fused<2>(p, st);
     case 4: return launch_pair_dz_fused<4>(p, st);
@@ -1746,8 +1740,20 @@ extern "C" int peneo_pair_dz_fused(int dtype, const void* ab_doc, int N, int D, 
     case 16: return launch_pair_dz_fused<16>(p, st);
     case 24: return launch_pair_dz_fused<24>(p, st);
     case 32: return launch_pair_dz_fused<32>(p, st);
-    default: set_error("peneo_pair_dz_fused: D=%d not supported (D/16 in {2,4,6,8,12,16,24,32})", D); return PENEO_ERR_INVALID;
+    default:
+      set_error("peneo_pair_dz_fused: D=%d not supported (D/16 in {2,4,6,8,12,16,24,32}, or 512 < D <= 1024 with D a multiple of 64)", D);
+      return PENEO_ERR_INVALID;
   }
+}
+
+// 1 exactly where peneo_pair_dz_fused has a kernel (host only, no GPU call)
+extern "C" int peneo_pair_dz_fused_supported(int dtype, int D, int num_heads) {
+  if (dtype != PENEO_BF16 || num_heads < 1 || num_heads > PENEO_MAX_HEADS || D <= 0) return 0;
+  if (D > 512) return pair_dz_wide_supported(dtype, D, num_heads) ? 1 : 0;
+  if (!pair_fwd_narrow_width(D)) return 0;
+  // the narrow kernel's LDS (launch_pair_dz_fused_v): ring, column table, sG and sPart
+  const size_t sh = (size_t)(D > 384 ? 2 : 3) * (size_t)slab_stride_bytes(D, 2) + (size_t)num_heads * D * 16 + (size_t)PH_WAVES * 32 * 16 * 3;
+  return sh <= 160 * 1024 ? 1 : 0;
 }
 
 // rows of peneo_pair_dz_fused's [rows][4 * nh*D] workspace for launches of up to `npairs` pairs, under the mode in force

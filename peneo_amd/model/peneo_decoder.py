@@ -470,6 +470,10 @@ class _DecoderStage(torch.autograd.Function):
         # peneo_pair_dz kernel: the GEMM's pair-dz epilogue does not regenerate the mask)
         fused_dz = (dec.fused_dz and dt == torch.bfloat16 and D % 32 == 0
                     and D // 16 in (2, 4, 6, 8, 12, 16, 24, 32))
+        # 512 < D <= 1024 (shrink off): the four-wave peneo_pair_dz_fused of pair_dz_wide.hip, opt-in (fused_dz_wide)
+        dz_wide = (not fused_dz and dec.fused_dz and dec.fused_dz_wide and dt == torch.bfloat16 and D > 512
+                   and ops.pair_dz_fused_supported(dt, D, nh))
+        fused_dz = fused_dz or dz_wide
         if fused_dz and dz_ws.shape[0] < ops.pair_dz_fused_workspace_rows(maxp):
             # (deterministic mode: peneo_pair_dz_fused gives every workgroup of a launch a workspace row of its own)
             dz_ws = torch.zeros((ops.pair_dz_fused_workspace_rows(maxp), 4 * nh * D), dtype=torch.float32, device=dev)
@@ -496,8 +500,11 @@ class _DecoderStage(torch.autograd.Function):
                 if fused_dz:
                     # dz straight from ab: x lives in registers, z in the MFMA accumulators; x / pre are only needed by
                     # the dW1 / dx GEMMs (measured best split of the two queues: x and dW1 on the main stream)
-                    ops.pair_x_fwd(ab[b], i0, i1, x, pre)
-                    ops.pair_dz_fused(ab[b], i0, i1, wp, b1cat, dza, z, dz_ws)
+                    if dz_wide and dec.dz_wide_writes_x:
+                        ops.pair_dz_fused(ab[b], i0, i1, wp, b1cat, dza, z, dz_ws, x, pre)
+                    else:
+                        ops.pair_x_fwd(ab[b], i0, i1, x, pre)
+                        ops.pair_dz_fused(ab[b], i0, i1, wp, b1cat, dza, z, dz_ws)
                     ops.gemm(z, x, a_kmajor=False, b_kmajor=False, out=dW1cat, accumulate=True)
                 else:
                     ops.pair_x_fwd(ab[b], i0, i1, x, pre)
@@ -754,6 +761,10 @@ class PEneoDecoder(nn.Module):
         self.fused_bwd = os.environ.get("PENEO_BWD_FUSED", "1") != "0"          # bf16: the whole pair-space backward in one kernel
         self.save_pair_act = os.environ.get("PENEO_PAIR_SAVE", "1") != "0"      # D = 384: the forward saves the classifiers' pre-activations
         self.pair_wide = os.environ.get("PENEO_PAIR_WIDE", "1") != "0"          # bf16, 512 < D <= 1024: the fused four-wave forward
+        # bf16, 512 < D <= 1024: the chunked backward takes the fused_dz branch on the four-wave peneo_pair_dz_fused (needs fused_dz).
+        # Off by default: DESIGN 28 has the measurement.  dz_wide_writes_x: that kernel also stores x / a_i + b_j (no peneo_pair_x_fwd launch)
+        self.fused_dz_wide = os.environ.get("PENEO_DZ_FUSED_WIDE", "0") == "1"
+        self.dz_wide_writes_x = os.environ.get("PENEO_DZ_WIDE_X", "0") == "1"
         self.dw1_on_side = os.environ.get("PENEO_DW1_SIDE", "1") != "0"          # its dW1 GEMM beside the following stages
         self.dw1_hold = os.environ.get("PENEO_DW1_HOLD", "1") != "0"             # ... joined at the end of the backward only
         self.dw1_side_split = int(os.environ.get("PENEO_DW1_SPLIT", "0"))   # fixed split-k of that GEMM; 0: from the targets below

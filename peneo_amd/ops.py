@@ -1145,6 +1145,12 @@ def pair_dz_fused_workspace_rows(npairs: int) -> int:
     return int(lib().peneo_pair_dz_fused_workspace_rows(int(npairs)))
 
 
+def pair_dz_fused_supported(dtype, D: int, num_heads: int) -> bool:
+    """``pair_dz_fused`` has a kernel for (dtype, D, heads): bf16 at D / 16 in {2, 4, 6, 8, 12, 16, 24, 32} and at 512 < D <= 1024 with
+    D % 64 == 0.  Host only."""
+    return bool(lib().peneo_pair_dz_fused_supported(dtype_code(dtype), int(D), int(num_heads)))
+
+
 def pair_dz_args(D: int, classes: Sequence[int], dlogits: Sequence[torch.Tensor], w2: Sequence[torch.Tensor],
                  scale: torch.Tensor, drop_p: float = 0.0, drop_seed: int = 0, drop_doc: int = 0,
                  drop_pair0: int = 0) -> "hip.PairDzArgs":
