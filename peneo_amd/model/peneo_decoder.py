@@ -12,8 +12,8 @@ from __future__ import annotations
 
 import os
 
-from dataclasses import dataclass
-from typing import List, Optional, Sequence, Tuple
+from dataclasses import dataclass, replace
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 import torch.nn as nn
@@ -196,39 +196,100 @@ def _row_chunks(n: int, max_pairs: int) -> List[Tuple[int, int]]:
     return out
 
 
+@dataclass(frozen=True)
+class PairRoute:
+    """Which kernels one step of the decoder stage runs for the pair heads (DESIGN 5 has the table).  ``pair_route`` decides it
+    once, in the forward; the backward dispatches on the route the forward stored and reads no switch of the decoder again, so a
+    switch changed between the forward and the backward of one step does not affect that step."""
+    forward: str                     # "generic" | "mxfp8_eval" | "mxfp8_save" | "bf16" (the compute dtype's kernel, fp32 included)
+    save: bool = False               # the forward leaves the classifiers' pre-activations and x for the "saved" backward ...
+    save_format: str = "f16"         # ... as "f16" or "e4m3" records
+    backward: Optional[str] = None   # "generic" | "saved" | "fused" | "chunked"; None: nothing to run (no gradients or no labels)
+    dz: Optional[str] = None         # "chunked" only, its dz producer: "fused" | "wide" | "epilogue" | "standalone"
+    writes_x: bool = False           # "wide" only: that kernel also stores x / a_i + b_j (no peneo_pair_x_fwd launch)
+
+
+def pair_route(dec: "PEneoDecoder", dt: torch.dtype, D: int, need_grad: bool, has_tags: bool, p_hidden: float) -> PairRoute:
+    """The route of a step at compute dtype `dt` and decoder width `D` from the decoder's switches and formats and the
+    library's host-side queries (no GPU).  p_hidden: the classifier dropout in force (DropoutSeeds.p_hidden)."""
+    nh = len(HEAD_NAMES)
+    train = need_grad and has_tags
+    if not dec.fused_pair_heads(dt, D):
+        # (classifier depths other than the shipped 2, widths without a fused pair-heads kernel: the materialising per-document path)
+        return PairRoute("generic", backward="generic" if train else None)
+    if dec.pair_heads_format == "mxfp8":
+        return PairRoute("mxfp8_eval")   # (PEneoDecoder.forward has refused a forward with gradients)
+    if not train:
+        return PairRoute("bf16")
+    if dec.fused_bwd and ops.pair_bwd_supported(dt, D, nh):   # (LDS: the head count enters, D = 512 holds 5 heads)
+        # the forward of such a step leaves the classifiers' pre-activations (dropout applied) and x in the backward's block order, 2
+        # bytes per pair and hidden unit (4.2 GB at 8 x 511 tokens): the backward repeats neither the first-layer product nor the mask
+        if not (dec.save_pair_act and ops.pair_save_supported(dt, D, nh)):
+            return PairRoute("bf16", backward="fused")
+        if dec.pair_heads_train_format == "mxfp8":   # (the same mask, the same saved buffers, the same backward: straight-through)
+            return PairRoute("mxfp8_save", save=True, backward="saved")
+        # (pair_save_e4m3_supported is pair_save_supported: whatever saves at all can save in either format)
+        return PairRoute("bf16", save=True, save_format="e4m3" if dec.pair_act_format == "e4m3" else "f16", backward="saved")
+    # the chunked backward: dz straight from ab by peneo_pair_dz_fused (the four-wave kernel above 512 only on request), else by the
+    # z GEMM's pair-dz epilogue - which does not regenerate the dropout mask: with it active, a plain GEMM and peneo_pair_dz
+    dz_kernel = dec.fused_dz and ops.pair_dz_fused_supported(dt, D, nh)
+    if dz_kernel and D <= 512:
+        return PairRoute("bf16", backward="chunked", dz="fused")
+    if dz_kernel and dec.fused_dz_wide:
+        return PairRoute("bf16", backward="chunked", dz="wide", writes_x=dec.dz_wide_writes_x)
+    return PairRoute("bf16", backward="chunked", dz="standalone" if p_hidden > 0.0 else "epilogue")
+
+
+def strict_refusal(dec: "PEneoDecoder", route: PairRoute, dt: torch.dtype, D: int) -> Optional[str]:
+    """The piece of a step on `route` that has no order-independent backward (deterministic mode 2 refuses it), or None."""
+    if dt != torch.bfloat16:
+        return "fp32 compute (the chunked decoder backward adds into d_ab and the pair_dz workspace with float atomics)"
+    if dec.num_cls_layers != 2:
+        return f"a {dec.num_cls_layers}-layer classifier (only the 2-layer heads have the fused backward; peneo_weighted_ce uses float atomics)"
+    if dec.le_loss.ohem:
+        return "OHEM (peneo_ohem_ce sums the kept pairs with float atomics)"
+    if not (route.backward in ("saved", "fused") or route.dz == "fused"):
+        return (f"the decoder backward at D = {D} without peneo_pair_bwd_fused and peneo_pair_dz_fused (the pair_dz GEMM epilogue "
+                "adds with float atomics)")
+
+
+class _StageParams(NamedTuple):
+    """`stage_params()` by name"""
+    shrink: Optional[tuple]          # (w0, b0, w3, b3) of the shrink MLP, None with the shrink off
+    wc_w: torch.Tensor
+    wc_b: torch.Tensor
+    heads: List[tuple]               # per head (w, b) x num_cls_layers, flat
+
+
+def _stage_params(dec: "PEneoDecoder", params: Sequence[torch.Tensor]) -> _StageParams:
+    at = 4 if dec.decoder_shrink else 0
+    k = 2 * dec.num_cls_layers
+    heads = [tuple(params[at + 2 + h * k:at + 2 + (h + 1) * k]) for h in range(len(HEAD_NAMES))]
+    return _StageParams(tuple(params[:4]) if dec.decoder_shrink else None, params[at], params[at + 1], heads)
+
+
 class _DecoderStage(torch.autograd.Function):
     """shrink MLP -> [a | b] projection -> fused pair heads (+ CE).  Inputs: cropped sequence output
-    [B*N, Hin]; outputs: total loss, 5 per-head losses, 5 logit maps."""
+    [B*N, Hin]; outputs: total loss, 5 per-head losses, 5 logit maps.  The pair heads run on one PairRoute, decided by the
+    forward and kept in ``saved["route"]`` (as run: without the saved form where its buffers did not fit)."""
 
     @staticmethod
     def forward(ctx, dec, seq, B, N, tags, want_logits, need_grad, *params):
-        wc, dt = dec.weight_cache, seq.dtype
-        it = iter(params)
-        if dec.decoder_shrink:
-            w0, b0, w3, b3 = next(it), next(it), next(it), next(it)
-        wc_w, wc_b = next(it), next(it)
-        kcls = dec.num_cls_layers
-        heads = [tuple(next(it) for _ in range(2 * kcls)) for _ in HEAD_NAMES]
-        D = wc_w.shape[0]
-        if need_grad and tags is not None and deterministic_mode() == 2:
-            # strict deterministic mode: say which piece of this step has no order-independent backward, before any of it runs
-            nh_ = len(HEAD_NAMES)
-            what = ("fp32 compute (the chunked decoder backward adds into d_ab and the pair_dz workspace with float atomics)"
-                    if dt != torch.bfloat16 else
-                    f"a {kcls}-layer classifier (only the 2-layer heads have the fused backward; peneo_weighted_ce uses float atomics)"
-                    if kcls != 2 else
-                    "OHEM (peneo_ohem_ce sums the kept pairs with float atomics)" if dec.le_loss.ohem else
-                    f"the decoder backward at D = {D} without peneo_pair_bwd_fused and peneo_pair_dz_fused (the pair_dz GEMM epilogue "
-                    "adds with float atomics)"
-                    if not ((dec.fused_bwd and ops.pair_bwd_supported(dt, D, nh_)) or
-                            (dec.fused_dz and D % 32 == 0 and D // 16 in (2, 4, 6, 8, 12, 16, 24, 32))) else None)
-            if what:
-                raise ValueError(f"deterministic mode 2 does not cover {what}; use mode 1 to run it and count it")
+        wc, dt, dev = dec.weight_cache, seq.dtype, seq.device
+        sp = _stage_params(dec, params)
+        D = sp.wc_w.shape[0]
+        # (DropoutSeeds.p_hidden, before the seeds are drawn: a refused step does not advance them)
+        route = pair_route(dec, dt, D, need_grad, tags is not None, float(dec.dropout_p) if dec.training else 0.0)
+        # strict deterministic mode: say which piece of this step has no order-independent backward, before any of it runs
+        what = strict_refusal(dec, route, dt, D) if need_grad and tags is not None and deterministic_mode() == 2 else None
+        if what:
+            raise ValueError(f"deterministic mode 2 does not cover {what}; use mode 1 to run it and count it")
         seeds = DropoutSeeds(dec.training, dec.dropout_p, 0.0)
-        dev = seq.device
-        saved = dict(seeds=seeds)
+        saved = dict(seeds=seeds, seq=seq, B=B, N=N, D=D, route=route)
+        ctx.dec, ctx.saved, ctx.params, ctx.has_loss = dec, saved, params, tags is not None
         h = seq
         if dec.decoder_shrink:
+            w0, b0, w3, b3 = sp.shrink
             W0, W3 = wc.cast("dec.s0", w0, dt), wc.cast("dec.s3", w3, dt)
             z1 = torch.empty((h.shape[0], w0.shape[0]), dtype=dt, device=dev)
             s1 = ops.gemm(h, W0, bias=b0, act=ACT_SILU, preact=z1, drop_p=seeds.p_hidden, drop_seed=seeds.seed(901))
@@ -238,52 +299,36 @@ class _DecoderStage(torch.autograd.Function):
             h = s2
         saved["s2"] = h
         # [a | b] = h [Wc[:, :D]; Wc[:, D:]]^T + [0 | bc]
-        Wab = dec.stacked_combine_weight(wc_w, dt)
-        bab = wc.cat_vec("dec.bab", [None, wc_b], [wc_b.numel(), wc_b.numel()])      # (zeros | bias)
-        ab = ops.gemm(h, Wab, bias=bab).view(B, N, 2 * D)
+        Wab = dec.stacked_combine_weight(sp.wc_w, dt)
+        bab = wc.cat_vec("dec.bab", [None, sp.wc_b], [sp.wc_b.numel(), sp.wc_b.numel()])      # (zeros | bias)
+        ab = saved["ab"] = ops.gemm(h, Wab, bias=bab).view(B, N, 2 * D)
         cws = [dec.le_loss.weight] + [dec.link_loss.weight] * 4 if tags is not None else None
-        if not dec.fused_pair_heads(dt, D):
-            # classifier depths other than the shipped 2 (reference :253-271) and widths without a fused pair-heads kernel (shrink off:
-            # fp32 above 512, any D / 16 outside the kernels' list): materialising per-document path
-            if kcls == 2 and tags is not None and dec.le_loss.ohem:
+        if route.forward == "generic":
+            if dec.num_cls_layers == 2 and tags is not None and dec.le_loss.ohem:
                 raise ValueError(f"OHEM runs behind the fused pair-heads kernel only, and there is none for {dt} at D = {D}")
-            logits, outs, extra = _generic_heads_forward(dec, ab, heads, tags, cws, seeds, need_grad, want_logits)
+            logits, outs, extra = _generic_heads_forward(dec, ab, sp.heads, tags, cws, seeds, need_grad, want_logits)
             saved.update(extra)
-            saved.update(ab=ab, B=B, N=N, D=D, seq=seq, generic_heads=True)
-            ctx.dec, ctx.saved, ctx.params = dec, saved, params
-            ctx.has_loss = tags is not None
-            ctx.mark_non_differentiable(*[lg for lg in logits if lg is not None])
-            ctx.set_materialize_grads(False)
-            return tuple(outs) + tuple(logits)
-        w1s, b1s = [hd[0] for hd in heads], [hd[1] for hd in heads]
-        w2s, b2s = [hd[2] for hd in heads], [hd[3] for hd in heads]
+            return _DecoderStage._outputs(ctx, outs, logits)
+        w1s, b1s = [hd[0] for hd in sp.heads], [hd[1] for hd in sp.heads]
+        w2s, b2s = [hd[2] for hd in sp.heads], [hd[3] for hd in sp.heads]
         b1cat = wc.cat_vec("dec.b1", b1s, [b.numel() for b in b1s])
         b2cat = wc.cat_vec("dec.b2", b2s, [b.numel() for b in b2s])
-        if dec.pair_heads_format == "mxfp8":
-            # eval-only MXFP8 first layer (PEneoDecoder.forward has refused a forward with gradients); its own pack and cache key
+        pack_mxfp8 = lambda: wc.get(("dec.pack_mxfp8",), w1s + w2s, lambda: ops.pair_heads_pack_mxfp8(   # (its own pack and cache key)
+            [w.detach() for w in w1s], [w.detach() for w in w2s]))
+        if route.forward == "mxfp8_eval":
             assert not need_grad
-            wpm = wc.get(("dec.pack_mxfp8",), w1s + w2s, lambda: ops.pair_heads_pack_mxfp8([w.detach() for w in w1s],
-                                                                                         [w.detach() for w in w2s]))
-            res = ops.pair_heads_fwd_mxfp8(ab, wpm, b1cat, b2cat, HEAD_CLASSES, want_logits=want_logits, tags=tags,
+            res = ops.pair_heads_fwd_mxfp8(ab, pack_mxfp8(), b1cat, b2cat, HEAD_CLASSES, want_logits=want_logits, tags=tags,
                                            class_weights=cws)
-            return _DecoderStage._finish(ctx, dec, saved, params, res, tags, cws, ab, B, N, D, seq, dev)
+            return _DecoderStage._finish(ctx, res, tags, cws)
         # the Dropout between the two layers of every classifier (reference :261) acts on the [B, P, 5D] hidden inside the
         # kernel; the backward regenerates the mask from (p, seed)
         saved["k12_drop"] = (seeds.p_hidden, seeds.seed(903))
-        # a step that will run the fused backward lets the forward leave the classifiers' pre-activations (f16, dropout applied) and
-        # x in the backward's block order: what autograd under autocast would have saved of reference :253-271, 2 bytes per pair and
-        # hidden unit (4.2 GB at 8 x 511 tokens) - the backward then neither repeats the first-layer product nor the dropout chain
-        save = (need_grad and tags is not None and dec.fused_bwd and dec.save_pair_act and ops.pair_bwd_supported(dt, D, len(HEAD_NAMES))
-                and ops.pair_save_supported(dt, D, len(HEAD_NAMES)))
-        # opt-in e4m3 records (set_pair_act_format): one byte per pair and hidden unit, half the buffer and half the stream
-        # (pair_save_e4m3_supported is pair_save_supported: whatever saves at all can save in either format)
-        act_e4m3 = save and dec.pair_act_format == "e4m3"
         bufs = None
-        if save:
+        if route.save:
             # (step-sized buffers are kept between steps: engine.big_acquire.)  The saved form is an optimisation that costs memory:
             # when its buffers do not fit, the step continues on the recomputing backward, which needs none of them
             try:
-                act_bytes = (ops.pair_save_e4m3_bytes if act_e4m3 else ops.pair_save_bytes)(B, N, len(HEAD_NAMES), D)
+                act_bytes = (ops.pair_save_e4m3_bytes if route.save_format == "e4m3" else ops.pair_save_bytes)(B, N, len(HEAD_NAMES), D)
                 act, act_h = big_acquire("pair_act", (act_bytes,), torch.uint8, dev)
                 try:
                     xr, xr_h = big_acquire("pair_x", (B * ops.pair_bwd_rows(N), D), dt, dev)
@@ -292,32 +337,29 @@ class _DecoderStage(torch.autograd.Function):
                     raise
                 bufs = (act, xr)
                 saved["pair_act"], saved["pair_x"] = (act, act_h), (xr, xr_h)
-                saved["pair_act_format"] = "e4m3" if act_e4m3 else "f16"
             except torch.cuda.OutOfMemoryError:
                 big_clear(dev)
-                save = False
-        if save and dec.pair_heads_train_format == "mxfp8":
-            # opt-in MXFP8 train forward (set_pair_heads_train_format): the first layer on block-scaled e4m3, the same mask and the same
-            # saved buffers; the backward below is unchanged, so its gradients are straight-through on the bf16 weights
-            wpm = wc.get(("dec.pack_mxfp8",), w1s + w2s, lambda: ops.pair_heads_pack_mxfp8([w.detach() for w in w1s],
-                                                                                         [w.detach() for w in w2s]))
-            res = ops.pair_heads_fwd_mxfp8_save(ab, wpm, b1cat, b2cat, HEAD_CLASSES, want_logits=want_logits, tags=tags,
+                route = saved["route"] = replace(route, forward="bf16", save=False, save_format="f16", backward="fused")
+        if route.forward == "mxfp8_save":
+            res = ops.pair_heads_fwd_mxfp8_save(ab, pack_mxfp8(), b1cat, b2cat, HEAD_CLASSES, want_logits=want_logits, tags=tags,
                                                 class_weights=cws, want_dlogits=True, drop_p=seeds.p_hidden,
                                                 drop_seed=seeds.seed(903), save_buffers=bufs)
-            return _DecoderStage._finish(ctx, dec, saved, params, res, tags, cws, ab, B, N, D, seq, dev)
+            return _DecoderStage._finish(ctx, res, tags, cws)
         wp = wc.get(("dec.pack", dt), w1s + w2s, lambda: ops.pair_heads_pack(dt, [w.detach() for w in w1s],
                                                                              [w.detach() for w in w2s]))
         res = ops.pair_heads_fwd(ab, wp, b1cat, b2cat, HEAD_CLASSES, want_logits=want_logits,
                                  tags=tags, class_weights=cws, want_dlogits=need_grad and tags is not None,
-                                 drop_p=seeds.p_hidden, drop_seed=seeds.seed(903), save=save, save_buffers=bufs,
-                                 save_format="e4m3" if save and act_e4m3 else "f16")
-        return _DecoderStage._finish(ctx, dec, saved, params, res, tags, cws, ab, B, N, D, seq, dev)
+                                 drop_p=seeds.p_hidden, drop_seed=seeds.seed(903), save=route.save, save_buffers=bufs,
+                                 save_format=route.save_format)
+        return _DecoderStage._finish(ctx, res, tags, cws)
 
     @staticmethod
-    def _finish(ctx, dec, saved, params, res, tags, cws, ab, B, N, D, seq, dev):
-        """losses from the pair kernel's logits / partial rows (both formats) and the autograd bookkeeping"""
+    def _finish(ctx, res, tags, cws):
+        """losses from the pair kernel's logits / partial rows (both formats)"""
+        dec, saved = ctx.dec, ctx.saved
+        dev = saved["ab"].device
         logits, partials, dlog = res[:3]
-        outs = []
+        outs = [None] * 6
         if tags is not None and dec.le_loss.ohem:
             # OHEM: the kept pairs of each head are chosen from its finished logit map; the un-normalised dlogits of the
             # dropped pairs are zeroed in place, so the backward below runs unchanged with scale_h = ratio_h / (k_pos + k_neg)
@@ -332,20 +374,16 @@ class _DecoderStage(torch.autograd.Function):
                                     workspace=ws)
                 off += c
             losses, scale = ops.ohem_finish(out8, ratio)
-            outs = [losses[5]] + [losses[i] for i in range(5)]
-            saved.update(scale=scale[0], inv_den=scale[1], dlog=dlog, dls=dls)
         elif tags is not None:
-            ratio = dec.loss_ratio_tensor(dev)
-            losses, scale, dls = ops.loss_finish(partials, ratio, sum(HEAD_CLASSES))
+            losses, scale, dls = ops.loss_finish(partials, dec.loss_ratio_tensor(dev), sum(HEAD_CLASSES))
+        if tags is not None:
             outs = [losses[5]] + [losses[i] for i in range(5)]
             saved.update(scale=scale[0], inv_den=scale[1], dlog=dlog, dls=dls)
-        else:
-            outs = [None] * 6
-        saved.update(ab=ab, B=B, N=N, D=D, seq=seq)
-        ctx.dec, ctx.saved, ctx.params = dec, saved, params
-        ctx.has_loss = tags is not None
-        if logits is None:
-            logits = [None] * 5
+        return _DecoderStage._outputs(ctx, outs, logits if logits is not None else [None] * 5)
+
+    @staticmethod
+    def _outputs(ctx, outs, logits):
+        """the stage's return value and what autograd has to know about it"""
         # ONE call: each call replaces ctx.non_differentiable.  The logits carry no gradient (the CE is fused into the
         # kernel that produces them), so a loss built on them outside the model raises instead of training on zeros.
         ctx.mark_non_differentiable(*[lg for lg in logits if lg is not None])
@@ -354,20 +392,10 @@ class _DecoderStage(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_loss, d_le=None, d_elh=None, d_elt=None, d_lgh=None, d_lgt=None, *unused):
-        dec, sv, params = ctx.dec, ctx.saved, ctx.params
+        dec, sv = ctx.dec, ctx.saved
         if not ctx.has_loss:
             raise PeneoHipError("backward through the PEneo decoder needs the five *_shaking_tag label maps")
-        wc = dec.weight_cache
-        it = iter(params)
-        if dec.decoder_shrink:
-            w0, b0, w3, b3 = next(it), next(it), next(it), next(it)
-        wc_w, wc_b = next(it), next(it)
-        kcls = dec.num_cls_layers
-        heads = [tuple(next(it) for _ in range(2 * kcls)) for _ in HEAD_NAMES]
-        B, N, D = sv["B"], sv["N"], sv["D"]
-        ab, seeds = sv["ab"], sv["seeds"]
-        dt, dev = ab.dtype, ab.device
-        nh = len(HEAD_NAMES)
+        dev = sv["ab"].device
         # dlogits are un-normalised: scale_h = ratio_h / den_h, times the incoming d(loss); the five per-head losses are
         # ordinary differentiable outputs as in the reference (peneo_decoder.py:375-428): their own incoming gradients
         # enter head by head as d(head loss) / den_h = d_head * scale_h / ratio_h
@@ -377,87 +405,110 @@ class _DecoderStage(torch.autograd.Function):
             extra = torch.stack([d.to(torch.float32).reshape(()) if d is not None else torch.zeros((), device=dev)
                                  for d in d_heads])
             scale = scale + extra * sv["inv_den"]
-        if sv.get("generic_heads"):   # (what the forward ran: fused_pair_heads reads a switch that may have changed since)
-            d_ab, head_grads = _generic_heads_backward(dec, sv, heads, scale)
-            return _DecoderStage._front_backward(ctx, dec, sv, params, d_ab, head_grads)
+        route = sv["route"]                          # (what the forward ran: the decoder's switches may have changed since)
+        if route.backward == "generic":
+            d_ab, head_grads = _generic_heads_backward(dec, sv, _stage_params(dec, ctx.params).heads, scale)
+            return _DecoderStage._front_backward(ctx, d_ab, head_grads)
+        if route.backward == "chunked":
+            return _DecoderStage._backward_chunked(ctx, scale)
+        return _DecoderStage._backward_fused(ctx, scale)
+
+    @staticmethod
+    def _head_operands(ctx):
+        """What both forms of the two-layer backward start from: (w1s, W1cat [nh*D, D], b1cat, zeroed dW1cat, contiguous w2s)."""
+        dec, sv = ctx.dec, ctx.saved
+        heads = _stage_params(dec, ctx.params).heads
+        wc, D, ab = dec.weight_cache, sv["D"], sv["ab"]
         w1s, b1s = [hd[0] for hd in heads], [hd[1] for hd in heads]
-        w2s, b2s = [hd[2] for hd in heads], [hd[3] for hd in heads]
-        W1cat = wc.cat_rows("dec.w1cat", w1s, dt)                      # [nh*D, D]
+        W1cat = wc.cat_rows("dec.w1cat", w1s, ab.dtype)                      # [nh*D, D]
         b1cat = wc.cat_vec("dec.b1", b1s, [b.numel() for b in b1s])
-        dW1cat = torch.zeros((nh * D, D), dtype=torch.float32, device=dev)
-        P = N * (N + 1) // 2
-        w2d = [w.detach().contiguous() for w in w2s]
+        dW1cat = torch.zeros((len(heads) * D, D), dtype=torch.float32, device=ab.device)
+        return w1s, W1cat, b1cat, dW1cat, [hd[2].detach().contiguous() for hd in heads]
+
+    @staticmethod
+    def _backward_fused(ctx, scale):
+        """Routes "saved" and "fused".  ONE kernel for the whole batch: x, z, dz, du = dz W1 and the sums into d_a / d_b never leave
+        the chip except dz and x themselves (block order), which the one remaining GEMM dW1 = dz^T x reads back once."""
+        dec, sv, params = ctx.dec, ctx.saved, ctx.params
+        # (W1cat is not read here; looking it up keeps it among the working copies an emitting optimizer writes)
+        w1s, _, b1cat, dW1cat, w2d = _DecoderStage._head_operands(ctx)
+        B, N, D, ab = sv["B"], sv["N"], sv["D"], sv["ab"]
+        dt, dev = ab.dtype, ab.device
+        nh = len(HEAD_NAMES)
         drop_p, drop_seed = sv["k12_drop"]
-        use_fused_bwd = dec.fused_bwd and ops.pair_bwd_supported(dt, D, nh)   # (LDS: the head count enters, D = 512 holds 5 heads)
-        # rows the dz producers spread their partial sums over: 256 for the fused kernels / the GEMM epilogue, the full
-        # 1024 for the stand-alone peneo_pair_dz (the chunked path with the classifier dropout active)
-        # (the fused kernels under the deterministic mode: one row per workgroup of the launch, ops.pair_bwd_workspace asks the library)
-        dz_ws = ops.pair_bwd_workspace(B, N, nh, D, dev) if use_fused_bwd else \
-            ops.pair_dz_workspace(nh, D, dev, slots=256 if drop_p == 0.0 else None)
-        # the fused kernel overwrites d_ab; the chunked path accumulates into it
-        d_ab = (torch.empty if use_fused_bwd else torch.zeros)((B, N, 2 * D), dtype=torch.float32, device=dev)
-        if use_fused_bwd:
-            # ONE kernel for the whole batch: x, z, dz, du = dz W1 and the sums into d_a / d_b never leave the chip except
-            # dz and x themselves (block order), which the one remaining GEMM dW1 = dz^T x reads back once
-            wp2 = wc.get(("dec.pack2", dt), w1s, lambda: ops.pair_bwd_pack([w.detach() for w in w1s]))
-            rows = ops.pair_bwd_rows(N)
-            # (a kept buffer may still be read by an earlier decoder backward of THIS autograd run - two forwards summed into one loss -
-            # whose side-stream join is deferred to the end of the backward: join first; nothing is pending in the usual step)
-            join_pending()
-            dzbuf, dz_h = big_acquire("pair_dz", (B * rows, nh * D), dt, dev)
-            dza = ops.pair_dz_args(D, HEAD_CLASSES, sv["dlog"], w2d, scale, drop_p=drop_p, drop_seed=drop_seed)
-            if "pair_act" in sv:
-                xbuf1, x_h = sv.pop("pair_x")
-                act, act_h = sv.pop("pair_act")
-                ops.pair_bwd_saved(ab, wp2, dza, act, dzbuf, d_ab, dz_ws, act_format=sv["pair_act_format"])   # (what the forward wrote)
-                big_release("pair_act", act_h)           # (read by that launch only: the next forward's stores are ordered behind it)
-            else:
-                xbuf1, x_h = big_acquire("pair_x", (B * rows, D), dt, dev)
-                ops.pair_bwd_fused(ab, wp2, b1cat, dza, dzbuf, xbuf1, d_ab, dz_ws)
-            # dz and x are read by the dW1 GEMM below, on the side stream or here: whoever takes them next (the next step's forward /
-            # backward, on the main stream) is issued after this backward has ended, i.e. behind the join of that side stream
-            big_release("pair_dz", dz_h)
-            big_release("pair_x", x_h)
-            # dW1 = dz^T x (2 ms of pure MFMA work, needed by nobody until the optimizer) runs on the side stream beside the
-            # shrink-MLP backward and the first encoder layers, whose short kernels leave CUs idle; joined one stage later
-            if dec.dw1_on_side:
-                main = torch.cuda.current_stream()
-                side = dec.side_stream(dev)
-                ev = torch.cuda.Event()
-                ev.record(main)
-                with torch.cuda.stream(side):
-                    side.wait_event(ev)
-                    # few, long workgroups: the split a GEMM gets when it runs alone fills all 512 resident slots, and the
-                    # main stream's kernels then find no CU to be dispatched to until it ends (measured: the stage after the
-                    # decoder stood still for 1.8 ms).  About one workgroup on every second CU runs ~7 ms beside the whole
-                    # encoder backward instead and is joined when the backward ends (split 11 / 7 / 5 / 4 / 3: 18.56 /
-                    # 18.79 / 18.34 / 18.16 / 18.10 ms per step on one box).
-                    # Only when the join can wait for the end of the backward (fresh .grad tensors, no DDP hooks reading them).
-                    can_hold = dec.dw1_hold and can_defer(params)
-                    # (D = 512: 80 tiles, i.e. ONE workgroup per tile from that target, would run 23 ms - longer than the 24-layer
-                    # encoder backward it hides behind; no workgroup gets more than dw1_side_rows rows of K: split 2 / 3 / 4 / 6 at
-                    # config 4: 30.5 / 31.1 / 32.8 / 32.7 ms per step)
-                    # (where peneo_gemm runs this product on 384 x 192 one-per-CU tiles -- nh D = 1920 x D = 384: 10 tiles --
-                    # the count is 10 x split workgroups, dw1_side_big_wgs of them: DESIGN 23 has the sweep)
-                    if ops.gemm_nn384_takes(nh * D, D, B * rows, dt):
-                        tiles, wgs = (nh * D // 384) * (D // 192), dec.dw1_side_big_wgs
-                    else:
-                        tiles, wgs = -(-nh * D // 128) * -(-D // 128), dec.dw1_side_wgs
-                    # (not held, or on the main stream below: the step pays the launch's alone-time, and ops.gemm picks the split of
-                    # a launch that has the chip to itself - one round of CUs on the 384 x 192 tiles, choose_split_k_nn384)
-                    split = None if not can_hold else \
-                        dec.dw1_side_split or max(1, wgs // tiles, -(-B * rows // dec.dw1_side_rows))
-                    with ops.kernel_timer("dw1_gemm"):
-                        ops.gemm(dzbuf, xbuf1, a_kmajor=False, b_kmajor=False, out=dW1cat, split_k=split)
-                ctx.side_work = (side, (dzbuf, xbuf1, dW1cat, ab), can_hold)
-            else:
-                with ops.kernel_timer("dw1_gemm"):
-                    ops.gemm(dzbuf, xbuf1, a_kmajor=False, b_kmajor=False, out=dW1cat)
-            chunks = []
+        # (under the deterministic mode: one workspace row per workgroup of the launch, ops.pair_bwd_workspace asks the library)
+        dz_ws = ops.pair_bwd_workspace(B, N, nh, D, dev)
+        d_ab = torch.empty((B, N, 2 * D), dtype=torch.float32, device=dev)   # the fused kernel overwrites d_ab
+        wp2 = dec.weight_cache.get(("dec.pack2", dt), w1s, lambda: ops.pair_bwd_pack([w.detach() for w in w1s]))
+        rows = ops.pair_bwd_rows(N)
+        # (a kept buffer may still be read by an earlier decoder backward of THIS autograd run - two forwards summed into one loss -
+        # whose side-stream join is deferred to the end of the backward: join first; nothing is pending in the usual step)
+        join_pending()
+        dzbuf, dz_h = big_acquire("pair_dz", (B * rows, nh * D), dt, dev)
+        dza = ops.pair_dz_args(D, HEAD_CLASSES, sv["dlog"], w2d, scale, drop_p=drop_p, drop_seed=drop_seed)
+        if sv["route"].backward == "saved":
+            xbuf1, x_h = sv.pop("pair_x")
+            act, act_h = sv.pop("pair_act")
+            ops.pair_bwd_saved(ab, wp2, dza, act, dzbuf, d_ab, dz_ws, act_format=sv["route"].save_format)   # (what the forward wrote)
+            big_release("pair_act", act_h)           # (read by that launch only: the next forward's stores are ordered behind it)
         else:
-            chunks = _row_chunks(N, dec.bwd_chunk_pairs)
-        if not chunks:
-            return _DecoderStage._finish_backward(ctx, dec, sv, params, scale, dW1cat, dz_ws, d_ab, heads, w1s, b1s, w2s, b2s)
+            xbuf1, x_h = big_acquire("pair_x", (B * rows, D), dt, dev)
+            ops.pair_bwd_fused(ab, wp2, b1cat, dza, dzbuf, xbuf1, d_ab, dz_ws)
+        # dz and x are read by the dW1 GEMM below, on the side stream or here: whoever takes them next (the next step's forward /
+        # backward, on the main stream) is issued after this backward has ended, i.e. behind the join of that side stream
+        big_release("pair_dz", dz_h)
+        big_release("pair_x", x_h)
+        # dW1 = dz^T x (2 ms of pure MFMA work, needed by nobody until the optimizer) runs on the side stream beside the
+        # shrink-MLP backward and the first encoder layers, whose short kernels leave CUs idle; joined one stage later
+        if dec.dw1_on_side:
+            main = torch.cuda.current_stream()
+            side = dec.side_stream(dev)
+            ev = torch.cuda.Event()
+            ev.record(main)
+            with torch.cuda.stream(side):
+                side.wait_event(ev)
+                # few, long workgroups: the split a GEMM gets when it runs alone fills all 512 resident slots, and the
+                # main stream's kernels then find no CU to be dispatched to until it ends (measured: the stage after the
+                # decoder stood still for 1.8 ms).  About one workgroup on every second CU runs ~7 ms beside the whole
+                # encoder backward instead and is joined when the backward ends (split 11 / 7 / 5 / 4 / 3: 18.56 /
+                # 18.79 / 18.34 / 18.16 / 18.10 ms per step on one box).
+                # Only when the join can wait for the end of the backward (fresh .grad tensors, no DDP hooks reading them).
+                can_hold = dec.dw1_hold and can_defer(params)
+                # (D = 512: 80 tiles, i.e. ONE workgroup per tile from that target, would run 23 ms - longer than the 24-layer
+                # encoder backward it hides behind; no workgroup gets more than dw1_side_rows rows of K: split 2 / 3 / 4 / 6 at
+                # config 4: 30.5 / 31.1 / 32.8 / 32.7 ms per step)
+                # (where peneo_gemm runs this product on 384 x 192 one-per-CU tiles -- nh D = 1920 x D = 384: 10 tiles --
+                # the count is 10 x split workgroups, dw1_side_big_wgs of them: DESIGN 23 has the sweep)
+                if ops.gemm_nn384_takes(nh * D, D, B * rows, dt):
+                    tiles, wgs = (nh * D // 384) * (D // 192), dec.dw1_side_big_wgs
+                else:
+                    tiles, wgs = -(-nh * D // 128) * -(-D // 128), dec.dw1_side_wgs
+                # (not held, or on the main stream below: the step pays the launch's alone-time, and ops.gemm picks the split of
+                # a launch that has the chip to itself - one round of CUs on the 384 x 192 tiles, choose_split_k_nn384)
+                split = None if not can_hold else \
+                    dec.dw1_side_split or max(1, wgs // tiles, -(-B * rows // dec.dw1_side_rows))
+                with ops.kernel_timer("dw1_gemm"):
+                    ops.gemm(dzbuf, xbuf1, a_kmajor=False, b_kmajor=False, out=dW1cat, split_k=split)
+            ctx.side_work = (side, (dzbuf, xbuf1, dW1cat, ab), can_hold)
+        else:
+            with ops.kernel_timer("dw1_gemm"):
+                ops.gemm(dzbuf, xbuf1, a_kmajor=False, b_kmajor=False, out=dW1cat)
+        return _DecoderStage._finish_backward(ctx, scale, dW1cat, dz_ws, d_ab)
+
+    @staticmethod
+    def _backward_chunked(ctx, scale):
+        """Route "chunked": the pair activations re-created chunk by chunk (rows of the triangle), dz by the route's producer."""
+        dec, sv = ctx.dec, ctx.saved
+        w1s, W1cat, b1cat, dW1cat, w2d = _DecoderStage._head_operands(ctx)
+        B, N, D, ab, route = sv["B"], sv["N"], sv["D"], sv["ab"], sv["route"]
+        dt, dev = ab.dtype, ab.device
+        nh = len(HEAD_NAMES)
+        drop_p, drop_seed = sv["k12_drop"]
+        # rows the dz producers spread their partial sums over: 256 for the fused kernels / the GEMM epilogue, the full
+        # 1024 for the stand-alone peneo_pair_dz (the classifier dropout active)
+        dz_ws = ops.pair_dz_workspace(nh, D, dev, slots=256 if drop_p == 0.0 else None)
+        d_ab = torch.zeros((B, N, 2 * D), dtype=torch.float32, device=dev)   # the chunked path accumulates into d_ab
+        chunks = _row_chunks(N, dec.bwd_chunk_pairs)
         maxp = max((i1 * N - i1 * (i1 - 1) // 2) - (i0 * N - i0 * (i0 - 1) // 2) for i0, i1 in chunks)
         # Two-stage pipeline over the pair chunks on two HIP streams: stage 1 (x, z GEMM whose epilogue turns z into dz:
         # VALU-bound) runs one chunk ahead of stage 2 (dW1 and dx GEMMs + the scatter into d_ab: MFMA-bound), so the two
@@ -466,20 +517,14 @@ class _DecoderStage(torch.autograd.Function):
         prebuf = [torch.empty((maxp, D), dtype=dt, device=dev) for _ in range(2)]   # a_i + b_j: SiLU' source of the dx GEMM
         zbuf = [torch.empty((maxp, nh * D), dtype=dt, device=dev) for _ in range(2)]
         dxbuf = torch.empty((maxp, D), dtype=dt, device=dev)
-        # (with the classifier dropout active the un-fused form runs z = x W1^T + b1 as a plain GEMM and the stand-alone
-        # peneo_pair_dz kernel: the GEMM's pair-dz epilogue does not regenerate the mask)
-        fused_dz = (dec.fused_dz and dt == torch.bfloat16 and D % 32 == 0
-                    and D // 16 in (2, 4, 6, 8, 12, 16, 24, 32))
-        # 512 < D <= 1024 (shrink off): the four-wave peneo_pair_dz_fused of pair_dz_wide.hip, opt-in (fused_dz_wide)
-        dz_wide = (not fused_dz and dec.fused_dz and dec.fused_dz_wide and dt == torch.bfloat16 and D > 512
-                   and ops.pair_dz_fused_supported(dt, D, nh))
-        fused_dz = fused_dz or dz_wide
-        if fused_dz and dz_ws.shape[0] < ops.pair_dz_fused_workspace_rows(maxp):
+        dz_from_ab = route.dz in ("fused", "wide")     # peneo_pair_dz_fused, eight-wave or four-wave
+        if dz_from_ab and dz_ws.shape[0] < ops.pair_dz_fused_workspace_rows(maxp):
             # (deterministic mode: peneo_pair_dz_fused gives every workgroup of a launch a workspace row of its own)
             dz_ws = torch.zeros((ops.pair_dz_fused_workspace_rows(maxp), 4 * nh * D), dtype=torch.float32, device=dev)
-        if fused_dz:
-            wp = wc.get(("dec.pack", dt), w1s + w2s, lambda: ops.pair_heads_pack(dt, [w.detach() for w in w1s],
-                                                                                 [w.detach() for w in w2s]))
+        if dz_from_ab:
+            w2s = [hd[2] for hd in _stage_params(dec, ctx.params).heads]
+            wp = dec.weight_cache.get(("dec.pack", dt), w1s + w2s, lambda: ops.pair_heads_pack(dt, [w.detach() for w in w1s],
+                                                                                               [w.detach() for w in w2s]))
         main = torch.cuda.current_stream()
         side = main if os.environ.get("PENEO_DEC_STREAMS", "2") == "1" else dec.side_stream(dev)   # "1": strictly serial
         ready = [torch.cuda.Event() for _ in range(2)]
@@ -497,10 +542,10 @@ class _DecoderStage(torch.autograd.Function):
                     main.wait_event(done[k])         # stage 2 of chunk idx-2 has released x[k] / z[k]
                 dza = ops.pair_dz_args(D, HEAD_CLASSES, [sv["dlog"][h][b, p0:p1] for h in range(nh)], w2d, scale,
                                        drop_p=drop_p, drop_seed=drop_seed, drop_doc=b, drop_pair0=p0)
-                if fused_dz:
+                if dz_from_ab:
                     # dz straight from ab: x lives in registers, z in the MFMA accumulators; x / pre are only needed by
                     # the dW1 / dx GEMMs (measured best split of the two queues: x and dW1 on the main stream)
-                    if dz_wide and dec.dz_wide_writes_x:
+                    if route.writes_x:
                         ops.pair_dz_fused(ab[b], i0, i1, wp, b1cat, dza, z, dz_ws, x, pre)
                     else:
                         ops.pair_x_fwd(ab[b], i0, i1, x, pre)
@@ -508,7 +553,7 @@ class _DecoderStage(torch.autograd.Function):
                     ops.gemm(z, x, a_kmajor=False, b_kmajor=False, out=dW1cat, accumulate=True)
                 else:
                     ops.pair_x_fwd(ab[b], i0, i1, x, pre)
-                    if drop_p > 0.0:
+                    if route.dz == "standalone":
                         ops.gemm(x, W1cat, bias=b1cat, out=z)
                         ops.pair_dz(z, npairs, D, HEAD_CLASSES, None, None, dz_ws, None, args=dza)
                     else:
@@ -519,7 +564,7 @@ class _DecoderStage(torch.autograd.Function):
                     side.wait_event(ready[k])
                     if idx > 0:
                         side.wait_event(done_x)      # dxbuf is single-buffered: the previous chunk's scatter has read it
-                    if not fused_dz:
+                    if not dz_from_ab:
                         ops.gemm(z, x, a_kmajor=False, b_kmajor=False, out=dW1cat, accumulate=True)
                     # du = (dz W1) * SiLU'(a_i + b_j) in the GEMM epilogue, then plain segmented sums into d_a / d_b
                     ops.gemm(z, W1cat, b_kmajor=False, out=dx, grad_src=pre, grad_act=ACT_SILU)
@@ -528,11 +573,12 @@ class _DecoderStage(torch.autograd.Function):
                     done_x = done[k]
                 idx += 1
         main.wait_stream(side)
-        return _DecoderStage._finish_backward(ctx, dec, sv, params, scale, dW1cat, dz_ws, d_ab, heads, w1s, b1s, w2s, b2s)
+        return _DecoderStage._finish_backward(ctx, scale, dW1cat, dz_ws, d_ab)
 
     @staticmethod
-    def _finish_backward(ctx, dec, sv, params, scale, dW1cat, dz_ws, d_ab, heads, w1s, b1s, w2s, b2s):
+    def _finish_backward(ctx, scale, dW1cat, dz_ws, d_ab):
         """Second half of the two-layer backward: parameter gradients of the heads from the accumulated sums."""
+        sv = ctx.saved
         D = sv["D"]
         nh = len(HEAD_NAMES)
         dw2, db1cat = ops.pair_dz_finish(dz_ws, nh, D, HEAD_CLASSES)
@@ -548,28 +594,27 @@ class _DecoderStage(torch.autograd.Function):
             c = HEAD_CLASSES[h]
             head_grads += [dW1cat[h * D:(h + 1) * D], db1cat[h * D:(h + 1) * D], dw2[h], db2cat[off:off + c]]
             off += c
-        return _DecoderStage._front_backward(ctx, dec, sv, params, d_ab, head_grads, w1s)
+        return _DecoderStage._front_backward(ctx, d_ab, head_grads)
 
     @staticmethod
-    def _front_backward(ctx, dec, sv, params, d_ab, head_grads, w1s=()):
+    def _front_backward(ctx, d_ab, head_grads):
         """Back through the [a | b] projection and the shrink MLP; `head_grads`: the heads' parameter gradients in
         stage_params() order."""
+        dec, sv, params = ctx.dec, ctx.saved, ctx.params
         wc = dec.weight_cache
         B, N, D = sv["B"], sv["N"], sv["D"]
         ab, seeds = sv["ab"], sv["seeds"]
-        dt, dev = ab.dtype, ab.device
-        it = iter(params)
-        if dec.decoder_shrink:
-            w0, b0, w3, b3 = next(it), next(it), next(it), next(it)
-        wc_w, wc_b = next(it), next(it)
+        dt = ab.dtype
+        sp = _stage_params(dec, params)
         d_ab2 = ops.cast(d_ab.view(B * N, 2 * D), dt) if dt != torch.float32 else d_ab.view(B * N, 2 * D)
         s2 = sv["s2"]
-        Wab = dec.stacked_combine_weight(wc_w, dt)
+        Wab = dec.stacked_combine_weight(sp.wc_w, dt)
         dWab = ops.gemm(d_ab2, s2, a_kmajor=False, b_kmajor=False, out_dtype=torch.float32)     # [2D, D]
         d_wc = torch.cat([dWab[:D], dWab[D:]], dim=1)
         d_bc = ops.colsum(d_ab2[:, D:])
         grads = []
         if dec.decoder_shrink:
+            w0, b0, w3, b3 = sp.shrink
             W0, W3 = wc.cast("dec.s0", w0, dt), wc.cast("dec.s3", w3, dt)
             d_z2 = ops.gemm(d_ab2, Wab, b_kmajor=False, grad_src=sv["z2"], grad_act=ACT_SILU,
                             drop_p=seeds.p_hidden, drop_seed=seeds.seed(902))
@@ -587,12 +632,12 @@ class _DecoderStage(torch.autograd.Function):
         grads += list(head_grads)
         grads = tuple(g if p.requires_grad else None for g, p in zip(grads, params))
         side_work = getattr(ctx, "side_work", None)
-        if side_work is not None:
+        if side_work is not None:                    # (the dW1 GEMM of _backward_fused)
             side, keep, can_hold = side_work
             ctx.side_work = None
             if can_defer(params):
                 if can_hold:   # the data-parallel wrapper lays these out last: their data is complete only at the end of the backward
-                    mark_late(w1s)
+                    mark_late([hd[0] for hd in sp.heads])
                 defer_join(side, keep=keep, hold=can_hold)
             else:
                 torch.cuda.current_stream().wait_stream(side)
@@ -793,20 +838,11 @@ class PEneoDecoder(nn.Module):
         five classifiers on block-scaled e4m3 instead (peneo_pair_heads_fwd_mxfp8_save); the backward is unchanged, so the
         gradients are straight-through on the bf16 weights, taken at the forward's quantized z.  Independent of
         set_pair_heads_format (forwards without gradients).  Needs bf16 compute, the 2-layer classifiers, a width both the saved
-        backward and the MXFP8 kernel hold, and the saved backward switched on (save_pair_act / fused_bwd)."""
+        backward and the MXFP8 kernel hold, and the saved backward switched on (_check_saved_format)."""
         if fmt not in ("bf16", "mxfp8"):
             raise ValueError(f"unknown pair-heads train format {fmt!r} (expected 'bf16' or 'mxfp8')")
         if fmt == "mxfp8":
-            if compute_dtype != torch.bfloat16:
-                raise ValueError("the mxfp8 train format of the pair heads needs compute dtype torch.bfloat16")
-            if self.num_cls_layers != 2:
-                raise ValueError(f"the mxfp8 train format of the pair heads needs peneo_classifier_num_layers == 2, not {self.num_cls_layers}")
-            if not ops.pair_mxfp8_save_supported(self.decoder_hidden_size, len(HEAD_NAMES)):
-                raise ValueError(f"the mxfp8 train format of the pair heads does not support decoder width D = {self.decoder_hidden_size}")
-            if not (self.save_pair_act and self.fused_bwd):
-                raise ValueError("the mxfp8 train format of the pair heads feeds the saved backward: save_pair_act and fused_bwd must be on")
-            if self.pair_act_format == "e4m3":
-                raise ValueError("the mxfp8 train forward writes f16 records: switch back with set_pair_act_format('f16') first")
+            self._check_saved_format("mxfp8", compute_dtype, "switch back with set_pair_act_format('f16') first", setter=True)
         self.pair_heads_train_format = fmt
 
     def set_pair_act_format(self, fmt: str, compute_dtype: torch.dtype = torch.bfloat16) -> None:
@@ -814,7 +850,7 @@ class PEneoDecoder(nn.Module):
         as f16, 2 bytes per pair and hidden unit.  "e4m3": as e4m3fn bytes (peneo_pair_heads_fwd_save_e4m3 / peneo_pair_bwd_saved_e4m3;
         include/peneo_hip.h): half the buffer and half the bytes streamed; the forward's losses are unchanged, the backward takes
         SiLU and SiLU' at z rounded to 3 mantissa bits (|z| above 448 saturates).  Needs bf16 compute, the 2-layer classifiers, a width
-        the e4m3 form holds (384) and the saved backward switched on (save_pair_act / fused_bwd); not together with
+        the e4m3 form holds (384) and the saved backward switched on (_check_saved_format); not together with
         set_pair_heads_train_format("mxfp8"), whose kernel writes f16 records.
         Memory: the step-sized buffers are kept between steps and a kept buffer that is large enough is handed out again
         (engine.big_acquire), so a process that has already trained with "f16" keeps its full-sized buffer after the switch; the saving
@@ -822,17 +858,27 @@ class PEneoDecoder(nn.Module):
         if fmt not in ops.PAIR_ACT_FORMATS:
             raise ValueError(f"unknown pair activation format {fmt!r} (expected 'f16' or 'e4m3')")
         if fmt == "e4m3":
-            if compute_dtype != torch.bfloat16:
-                raise ValueError("the e4m3 pair activations need compute dtype torch.bfloat16")
-            if self.num_cls_layers != 2:
-                raise ValueError(f"the e4m3 pair activations need peneo_classifier_num_layers == 2, not {self.num_cls_layers}")
-            if not ops.pair_save_e4m3_supported(torch.bfloat16, self.decoder_hidden_size, len(HEAD_NAMES)):
-                raise ValueError(f"the e4m3 pair activations do not support decoder width D = {self.decoder_hidden_size}")
-            if not (self.save_pair_act and self.fused_bwd):
-                raise ValueError("the e4m3 pair activations are those of the saved backward: save_pair_act and fused_bwd must be on")
-            if self.pair_heads_train_format == "mxfp8":
-                raise ValueError("the mxfp8 train forward writes f16 records: switch back with set_pair_heads_train_format('bf16') first")
+            self._check_saved_format("e4m3", compute_dtype, "switch back with set_pair_heads_train_format('bf16') first", setter=True)
         self.pair_act_format = fmt
+
+    def _check_saved_format(self, fmt: str, dt: torch.dtype, way_out: str, setter: bool = False) -> None:
+        """What "mxfp8" (set_pair_heads_train_format) and "e4m3" (set_pair_act_format) need, both riding on the saved backward:
+        bf16 compute, save_pair_act and fused_bwd on, and not each other (`way_out`: what the message advises).  Checked by the
+        setters, which also check the classifier depth and the width, and again by every forward with gradients: what a setter
+        checked may have been changed since."""
+        mx = fmt == "mxfp8"
+        it, s, does = ("the mxfp8 train format of the pair heads", "s", "does") if mx else ("the e4m3 pair activations", "", "do")
+        D, nh = self.decoder_hidden_size, len(HEAD_NAMES)
+        if dt != torch.bfloat16:
+            raise ValueError(f"{it} need{s} compute dtype torch.bfloat16")
+        if setter and self.num_cls_layers != 2:
+            raise ValueError(f"{it} need{s} peneo_classifier_num_layers == 2, not {self.num_cls_layers}")
+        if setter and not (ops.pair_mxfp8_save_supported(D, nh) if mx else ops.pair_save_e4m3_supported(torch.bfloat16, D, nh)):
+            raise ValueError(f"{it} {does} not support decoder width D = {D}")
+        if not (self.save_pair_act and self.fused_bwd):
+            raise ValueError(f"{it} {'feeds' if mx else 'are those of'} the saved backward: save_pair_act and fused_bwd must be on")
+        if (self.pair_act_format == "e4m3") if mx else (self.pair_heads_train_format == "mxfp8"):
+            raise ValueError(f"the mxfp8 train forward writes f16 records: {way_out}")
 
     def fused_pair_heads(self, dt: torch.dtype, D: int) -> bool:
         """True where the forward runs the fused pair-heads kernel: the 2-layer classifiers at a (dtype, width) the library has one
@@ -910,19 +956,9 @@ class PEneoDecoder(nn.Module):
             if sequence_output.dtype != torch.bfloat16:
                 raise ValueError("mxfp8 pair heads need compute dtype torch.bfloat16")
         if self.pair_heads_train_format == "mxfp8" and need_grad:
-            # what set_pair_heads_train_format checked may have been changed since
-            if sequence_output.dtype != torch.bfloat16:
-                raise ValueError("the mxfp8 train format of the pair heads needs compute dtype torch.bfloat16")
-            if not (self.save_pair_act and self.fused_bwd):
-                raise ValueError("the mxfp8 train format of the pair heads feeds the saved backward: save_pair_act and fused_bwd must be on")
+            self._check_saved_format("mxfp8", sequence_output.dtype, "it cannot run with the e4m3 pair activations")
         if self.pair_act_format == "e4m3" and need_grad:
-            # what set_pair_act_format checked may have been changed since
-            if sequence_output.dtype != torch.bfloat16:
-                raise ValueError("the e4m3 pair activations need compute dtype torch.bfloat16")
-            if not (self.save_pair_act and self.fused_bwd):
-                raise ValueError("the e4m3 pair activations are those of the saved backward: save_pair_act and fused_bwd must be on")
-            if self.pair_heads_train_format == "mxfp8":
-                raise ValueError("the mxfp8 train forward writes f16 records: it cannot run with the e4m3 pair activations")
+            self._check_saved_format("e4m3", sequence_output.dtype, "it cannot run with the e4m3 pair activations")
         res = _DecoderStage.apply(self, sequence_output.reshape(B * N, Hin), B, N, tags, want_logits, need_grad, *params)
         loss, l_le, l_elh, l_elt, l_lgh, l_lgt, o_le, o_elh, o_elt, o_lgh, o_lgt = res
         if self.inference_mode:

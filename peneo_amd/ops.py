@@ -818,6 +818,58 @@ def pair_heads_pack(dtype: torch.dtype, w1: Sequence[torch.Tensor], w2: Sequence
     return packed
 
 
+def _pair_heads_launch(entry: str, timer: str, ab: torch.Tensor, wp: torch.Tensor, b1: torch.Tensor, b2: torch.Tensor,
+                       classes: Sequence[int], want_logits: bool, tags, class_weights, *, typed: bool = False,
+                       want_dlogits: bool = False, drop_p: float = 0.0, drop_seed: int = 0, save_bytes: Optional[int] = None,
+                       save_buffers=None):
+    """The one launch behind pair_heads_fwd / pair_heads_fwd_mxfp8 / pair_heads_fwd_mxfp8_save: fills PairHeadsDesc and PairLoss,
+    allocates what the caller asked for and calls `entry` under kernel_timer(`timer`).  typed: the entry point takes the dtype
+    code first.  save_bytes: the entry point is a saving one - loss partials in the saving launch's rows, and (act [>= save_bytes]
+    uint8, x_rows) checked (save_buffers) or allocated, passed on and returned as a fourth value."""
+    B, N, D2 = ab.shape
+    D = D2 // 2
+    P = N * (N + 1) // 2
+    nh = len(classes)
+    dev = ab.device
+    desc = hip.PairHeadsDesc()
+    desc.num_heads, desc.D = nh, D
+    for h, c in enumerate(classes):
+        desc.classes[h] = c
+    desc.w_packed, desc.b1, desc.b2 = ptr(wp), ptr(b1), ptr(b2)
+    desc.drop_p, desc.drop_seed = float(drop_p), int(drop_seed) & 0xFFFFFFFF
+    logits = [torch.empty((B, P, c), dtype=torch.float32, device=dev) for c in classes] if want_logits else None
+    loss = partials = dlog = None
+    if tags is not None:
+        loss = hip.PairLoss()
+        nrows = lib().peneo_pair_loss_partials_save(B, N) if save_bytes is not None else lib().peneo_pair_loss_partials(B, N)
+        partials = torch.empty((nrows, 32), dtype=torch.float32, device=dev)
+        if want_dlogits:
+            dlog = [torch.empty((B, P, c), dtype=torch.float32, device=dev) for c in classes]
+        for h in range(nh):
+            assert tags[h].dtype == torch.int64 and tags[h].shape == (B, P)
+            loss.tags[h] = ptr(_c(tags[h]))
+            loss.class_weight[h] = ptr(class_weights[h]) if class_weights is not None else None
+            if dlog is not None:
+                loss.dlogits[h] = ptr(dlog[h])
+        loss.partials = ptr(partials)
+    args = [dtype_code(ab.dtype)] if typed else []
+    args += [ptr(ab), B, N, C.byref(desc), _ptr_list(logits) if logits is not None else None, C.byref(loss) if loss is not None else None]
+    saved = ()
+    if save_bytes is not None:
+        if save_buffers is not None:
+            act, x_rows = save_buffers
+            assert act.dtype == torch.uint8 and act.numel() >= save_bytes and act.is_contiguous()
+            assert x_rows.shape == (B * pair_bwd_rows(N), D) and x_rows.dtype == ab.dtype and x_rows.is_contiguous()
+        else:
+            act = torch.empty(save_bytes, dtype=torch.uint8, device=dev)
+            x_rows = torch.empty((B * pair_bwd_rows(N), D), dtype=ab.dtype, device=dev)
+        args += [ptr(act), ptr(x_rows)]
+        saved = ((act, x_rows),)
+    with kernel_timer(timer):
+        check(getattr(lib(), entry)(*args, stream()), entry)
+    return (logits, partials, dlog) + saved
+
+
 def pair_heads_fwd(ab: torch.Tensor, wp: torch.Tensor, b1: torch.Tensor, b2: torch.Tensor,
                    classes: Sequence[int], *, want_logits: bool = True, tags: Optional[Sequence[torch.Tensor]] = None,
                    class_weights: Optional[Sequence[Optional[torch.Tensor]]] = None, want_dlogits: bool = False,
@@ -831,53 +883,15 @@ def pair_heads_fwd(ab: torch.Tensor, wp: torch.Tensor, b1: torch.Tensor, b2: tor
     if save_format not in PAIR_ACT_FORMATS:
         raise ValueError(f"save_format must be one of {PAIR_ACT_FORMATS}, got {save_format!r}")
     _c(ab)
-    B, N, D2 = ab.shape
-    D = D2 // 2
-    P = N * (N + 1) // 2
-    nh = len(classes)
-    desc = hip.PairHeadsDesc()
-    desc.num_heads, desc.D = nh, D
-    for h, c in enumerate(classes):
-        desc.classes[h] = c
-    desc.w_packed, desc.b1, desc.b2 = ptr(wp), ptr(b1), ptr(b2)
-    desc.drop_p, desc.drop_seed = float(drop_p), int(drop_seed) & 0xFFFFFFFF
-    logits = [torch.empty((B, P, c), dtype=torch.float32, device=ab.device) for c in classes] if want_logits else None
-    lp = _ptr_list(logits) if logits is not None else None
-    loss = None
-    partials = None
-    dlog = None
-    if tags is not None:
-        loss = hip.PairLoss()
-        nrows = lib().peneo_pair_loss_partials_save(B, N) if save else lib().peneo_pair_loss_partials(B, N)
-        partials = torch.empty((nrows, 32), dtype=torch.float32, device=ab.device)
-        if want_dlogits:
-            dlog = [torch.empty((B, P, c), dtype=torch.float32, device=ab.device) for c in classes]
-        for h in range(nh):
-            assert tags[h].dtype == torch.int64 and tags[h].shape == (B, P)
-            loss.tags[h] = ptr(_c(tags[h]))
-            loss.class_weight[h] = ptr(class_weights[h]) if class_weights is not None else None
-            if dlog is not None:
-                loss.dlogits[h] = ptr(dlog[h])
-        loss.partials = ptr(partials)
+    entry, nbytes = "peneo_pair_heads_fwd", None
     if save:
+        B, N, D2 = ab.shape
         e4m3 = save_format == "e4m3"
-        nbytes = lib().peneo_pair_save_e4m3_bytes(B, N, nh, D) if e4m3 else lib().peneo_pair_save_bytes(B, N, nh, D)
-        if save_buffers is not None:
-            act, x_rows = save_buffers
-            assert act.dtype == torch.uint8 and act.numel() >= nbytes and act.is_contiguous()
-            assert x_rows.shape == (B * pair_bwd_rows(N), D) and x_rows.dtype == ab.dtype and x_rows.is_contiguous()
-        else:
-            act = torch.empty(nbytes, dtype=torch.uint8, device=ab.device)
-            x_rows = torch.empty((B * pair_bwd_rows(N), D), dtype=ab.dtype, device=ab.device)
         entry = "peneo_pair_heads_fwd_save_e4m3" if e4m3 else "peneo_pair_heads_fwd_save"
-        with kernel_timer("pair_heads_fwd"):
-            check(getattr(lib(), entry)(dtype_code(ab.dtype), ptr(ab), B, N, C.byref(desc), lp,
-                                        C.byref(loss) if loss is not None else None, ptr(act), ptr(x_rows), stream()), entry)
-        return logits, partials, dlog, (act, x_rows)
-    with kernel_timer("pair_heads_fwd"):
-        check(lib().peneo_pair_heads_fwd(dtype_code(ab.dtype), ptr(ab), B, N, C.byref(desc), lp,
-                                         C.byref(loss) if loss is not None else None, stream()), "peneo_pair_heads_fwd")
-    return logits, partials, dlog
+        nbytes = (lib().peneo_pair_save_e4m3_bytes if e4m3 else lib().peneo_pair_save_bytes)(B, N, len(classes), D2 // 2)
+    return _pair_heads_launch(entry, "pair_heads_fwd", ab, wp, b1, b2, classes, want_logits, tags, class_weights, typed=True,
+                              want_dlogits=want_dlogits, drop_p=drop_p, drop_seed=drop_seed, save_bytes=nbytes,
+                              save_buffers=save_buffers)
 
 
 PAIR_ACT_FORMATS = ("f16", "e4m3")      # record formats of the saved pair activations (include/peneo_hip.h)
@@ -1030,32 +1044,8 @@ def pair_heads_fwd_mxfp8(ab: torch.Tensor, wp: torch.Tensor, b1: torch.Tensor, b
     Returns (logits list | None, loss partials [n, 32] | None, None) like pair_heads_fwd without dlogits."""
     _c(ab)
     assert ab.dtype == torch.bfloat16, "pair_heads_fwd_mxfp8 takes bf16 ab"
-    B, N, D2 = ab.shape
-    D = D2 // 2
-    P = N * (N + 1) // 2
-    nh = len(classes)
-    desc = hip.PairHeadsDesc()
-    desc.num_heads, desc.D = nh, D
-    for h, c in enumerate(classes):
-        desc.classes[h] = c
-    desc.w_packed, desc.b1, desc.b2 = ptr(wp), ptr(b1), ptr(b2)
-    desc.drop_p, desc.drop_seed = 0.0, 0
-    logits = [torch.empty((B, P, c), dtype=torch.float32, device=ab.device) for c in classes] if want_logits else None
-    lp = _ptr_list(logits) if logits is not None else None
-    loss = None
-    partials = None
-    if tags is not None:
-        loss = hip.PairLoss()
-        partials = torch.empty((lib().peneo_pair_loss_partials(B, N), 32), dtype=torch.float32, device=ab.device)
-        for h in range(nh):
-            assert tags[h].dtype == torch.int64 and tags[h].shape == (B, P)
-            loss.tags[h] = ptr(_c(tags[h]))
-            loss.class_weight[h] = ptr(class_weights[h]) if class_weights is not None else None
-        loss.partials = ptr(partials)
-    with kernel_timer("pair_heads_fwd_mxfp8"):
-        check(lib().peneo_pair_heads_fwd_mxfp8(ptr(ab), B, N, C.byref(desc), lp, C.byref(loss) if loss is not None else None,
-                                               stream()), "peneo_pair_heads_fwd_mxfp8")
-    return logits, partials, None
+    return _pair_heads_launch("peneo_pair_heads_fwd_mxfp8", "pair_heads_fwd_mxfp8", ab, wp, b1, b2, classes, want_logits, tags,
+                              class_weights)
 
 
 def pair_mxfp8_save_supported(D: int, num_heads: int) -> bool:
@@ -1074,47 +1064,15 @@ def pair_heads_fwd_mxfp8_save(ab: torch.Tensor, wp: torch.Tensor, b1: torch.Tens
     assert ab.dtype == torch.bfloat16, "pair_heads_fwd_mxfp8_save takes bf16 ab"
     B, N, D2 = ab.shape
     D = D2 // 2
-    P = N * (N + 1) // 2
     nh = len(classes)
     if not pair_mxfp8_save_supported(D, nh):
         raise ValueError(f"MXFP8 train forward of the pair heads: D={D} with {nh} heads is not supported")
     # the C entry point takes a pointer without a size: a bf16 pack (twice the bytes) is caught here
     if wp.dtype != torch.uint8 or wp.numel() != lib().peneo_pair_heads_mxfp8_packed_bytes(nh, D):
         raise ValueError("pair_heads_fwd_mxfp8_save: wp is not a pair_heads_pack_mxfp8 buffer for this shape")
-    desc = hip.PairHeadsDesc()
-    desc.num_heads, desc.D = nh, D
-    for h, c in enumerate(classes):
-        desc.classes[h] = c
-    desc.w_packed, desc.b1, desc.b2 = ptr(wp), ptr(b1), ptr(b2)
-    desc.drop_p, desc.drop_seed = float(drop_p), int(drop_seed) & 0xFFFFFFFF
-    logits = [torch.empty((B, P, c), dtype=torch.float32, device=ab.device) for c in classes] if want_logits else None
-    lp = _ptr_list(logits) if logits is not None else None
-    loss = None
-    partials = None
-    dlog = None
-    if tags is not None:
-        loss = hip.PairLoss()
-        partials = torch.empty((lib().peneo_pair_loss_partials_save(B, N), 32), dtype=torch.float32, device=ab.device)
-        if want_dlogits:
-            dlog = [torch.empty((B, P, c), dtype=torch.float32, device=ab.device) for c in classes]
-        for h in range(nh):
-            assert tags[h].dtype == torch.int64 and tags[h].shape == (B, P)
-            loss.tags[h] = ptr(_c(tags[h]))
-            loss.class_weight[h] = ptr(class_weights[h]) if class_weights is not None else None
-            if dlog is not None:
-                loss.dlogits[h] = ptr(dlog[h])
-        loss.partials = ptr(partials)
-    if save_buffers is not None:
-        act, x_rows = save_buffers
-        assert act.dtype == torch.uint8 and act.numel() >= lib().peneo_pair_save_bytes(B, N, nh, D) and act.is_contiguous()
-        assert x_rows.shape == (B * pair_bwd_rows(N), D) and x_rows.dtype == ab.dtype and x_rows.is_contiguous()
-    else:
-        act = torch.empty(lib().peneo_pair_save_bytes(B, N, nh, D), dtype=torch.uint8, device=ab.device)
-        x_rows = torch.empty((B * pair_bwd_rows(N), D), dtype=ab.dtype, device=ab.device)
-    with kernel_timer("pair_heads_fwd_mxfp8_save"):
-        check(lib().peneo_pair_heads_fwd_mxfp8_save(ptr(ab), B, N, C.byref(desc), lp, C.byref(loss) if loss is not None else None,
-                                                    ptr(act), ptr(x_rows), stream()), "peneo_pair_heads_fwd_mxfp8_save")
-    return logits, partials, dlog, (act, x_rows)
+    return _pair_heads_launch("peneo_pair_heads_fwd_mxfp8_save", "pair_heads_fwd_mxfp8_save", ab, wp, b1, b2, classes, want_logits,
+                              tags, class_weights, want_dlogits=want_dlogits, drop_p=drop_p, drop_seed=drop_seed,
+                              save_bytes=lib().peneo_pair_save_bytes(B, N, nh, D), save_buffers=save_buffers)
 
 
 def pair_x_fwd(ab_doc: torch.Tensor, i0: int, i1: int, out: torch.Tensor, pre: Optional[torch.Tensor] = None) -> torch.Tensor:
