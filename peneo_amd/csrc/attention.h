@@ -1,4 +1,6 @@
-// Shared between attention.hip and attn_bwd_pipe.hip: the parameter block of the attention kernels.
+// Shared between attention.hip and the pipelined attn_fwd_pipe.hip / attn_bwd_pipe.hip (attn2_bwd_pipe.hip takes attn_kslot from
+// here): the parameter block of the attention kernels, the keep-word slot order and the pipelined launchers.  The device
+// primitives the kernels share are in attn_pipe.h.
 #pragma once
 #include "common.h"
 

@@ -17,16 +17,14 @@
 // tile ahead of the MFMAs.  The additive bias [B, nh, T, Tp] (row stride Tp = T rounded up to 64,
 // padding and masked keys = -1e30) is staged through LDS the same way.  Soft-max runs in the exp2
 // domain in fp32.  scores = scale * q.k + bias (reference: modeling_layoutlmv3.py:365-389).
-#include <cstdlib>
 #include "common.h"
 #include "attention.h"
+#include "attn_pipe.h"
 
 namespace peneo {
 
 constexpr int AQ = 128;   // rows of the "n" side per workgroup (4 waves x 32)
 constexpr int AK = 64;    // rows of the streamed side per tile
-constexpr float MASKED = -1.0e30f;
-constexpr float LOG2E = 1.4426950408889634f;
 // raw v_exp_f32: arguments here are <= 0 (or hugely negative for masked keys), results in [0, 1]; no denormal fix-up needed
 __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 
@@ -49,31 +47,8 @@ __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_ex
 __device__ __forceinline__ bool attn_word_keep(const uint32_t* words_bh, int Tk, int q, int key) {
   return (words_bh[(int64_t)(q >> 5) * Tk + attn_kslot(key)] >> (q & 31)) & 1u;
 }
-// x where the lane's bit of the 64-bit mask is set, else 0 (mask in an SGPR pair).  s_nop 1: the pair comes from v_readlane,
-// and gfx950 wants two wait states between a VALU write of an SGPR and a VALU read of it; the compiler pads that hazard for
-// instructions it can see, not inside inline asm (the fp32 kernel's schedule put the two back to back: wrong masks)
-__device__ __forceinline__ float mask_keep(float x, uint64_t m) {
-  float r;
-  asm("s_nop 1\n\tv_cndmask_b32_e64 %0, 0, %1, %2" : "=v"(r) : "v"(x), "s"(m));
-  return r;
-}
-// register mask i of a forward tile from the wave's 64 keep words (lane L holds word L of the tile): two v_readlane into
-// an SGPR pair.  (Scalar loads of the words straight into SGPRs were tried first: left to the compiler they sit right in
-// front of the first use with a full s_waitcnt each - SMEM returns out of order - and the forward ran slower than with the
-// hash; issued by hand at the top of the tile, the register allocator spilled the destination SGPRs between the load and
-// the wait, i.e. before the data had arrived.)
-__device__ __forceinline__ uint64_t lane_words_mask(uint32_t w, int word /* even, wave-uniform */) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)w, word), hi = (uint32_t)__builtin_amdgcn_readlane((int)w, word + 1);
-  return (uint64_t)lo | ((uint64_t)hi << 32);
-#else
-  return 0;
-#endif
-}
-__device__ __forceinline__ float and_mask(float x, int m) { return __uint_as_float(__float_as_uint(x) & (uint32_t)m); }
-// the running maximum of the online softmax only moves when a tile beats it by more than this (natural units): exponentials
-// stay below e^4 and the rescaling of the accumulators - one multiply per element - is skipped for almost every tile
-constexpr float RESCALE_TAU = 4.0f;
+// (mask_keep, lane_words_mask, and_u: attn_pipe.h)
+__device__ __forceinline__ float and_mask(float x, int m) { return __uint_as_float(and_u(x, m)); }
 
 __global__ __launch_bounds__(256) void attn_drop_words_kernel(uint32_t* words, int64_t n, uint32_t thr16, uint32_t seed) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
@@ -128,17 +103,13 @@ template <int COLS> struct FragReader<float, COLS> {
   }
 };
 
-typedef short s16x4_t __attribute__((ext_vector_type(4)));
 // fragment for an MFMA operand whose row index is the contiguous LDS dimension: rows (lane&31) + col0, reduction
 // indices {k0..k0+3} and {k1..k1+3} (LDS rows) -> two transpose reads of a [4 k][16 rows] block per 16-lane group
 template <int PITCH>
 __device__ __forceinline__ Frag<bf16_t> frag_tr(const char* tile, int col0, int k0, int k1, int lane) {
-  typedef __attribute__((address_space(3))) s16x4_t* lds_s4p;
   const int c = col0 + 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
   const int kr = (lane & 15) >> 2;
-  s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4p)(tile + (k0 + kr) * PITCH + c * 2));
-  s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4p)(tile + (k1 + kr) * PITCH + c * 2));
-  uint2 l2 = __builtin_bit_cast(uint2, lo), h2 = __builtin_bit_cast(uint2, hi);
+  const uint2 l2 = tr64(tile + (k0 + kr) * PITCH + c * 2), h2 = tr64(tile + (k1 + kr) * PITCH + c * 2);
   Frag<bf16_t> f;
   f.v = make_uint4(l2.x, l2.y, h2.x, h2.y);
   return f;
@@ -351,7 +322,7 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 && DP <= 64) ? (FK == 32 ? 3 :
   for (int t = 0; t < DT; ++t)
 #pragma unroll
     for (int r = 0; r < 16; ++r) o[t][r] = 0.f;
-  float m_run = MASKED, l_run = 0.f;
+  float m_run = kMasked, l_run = 0.f;
 
   TileRegs<T, FK, DP> rk;
   TileRegs<T, DP, FK> rv;
@@ -375,7 +346,7 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 && DP <= 64) ? (FK == 32 ? 3 :
     tile_store<T, FK, DP>(rk, sK, tid);
     if constexpr (VTR) tile_store<T, FK, DP>(rv2, sVt, tid); else tile_store<T, DP, FK>(rv, sVt, tid);
     if (bias) bias_store<T, AQ, FK>(rb, sB, tid);
-    if (tid < FK) sKb[tid] = (k0 + tid < Tn) ? (kb ? kb[k0 + tid] : 0.f) : MASKED;
+    if (tid < FK) sKb[tid] = (k0 + tid < Tn) ? (kb ? kb[k0 + tid] : 0.f) : kMasked;
     __syncthreads();
     const uint32_t cw = rw;                   // this tile's keep words (lane L: word L of its 64-key group)
     const int wsel = (FK == 32) ? 32 * (t & 1) : 0;   // 32-key tiles: the odd tile uses the group's second half
@@ -394,7 +365,7 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 && DP <= 64) ? (FK == 32 ? 3 :
         Frag<T> kf = FragReader<T, DP>::straight(sK, kt * 32 + (lane & 31), 16 * ks + 8 * half);
         mma_step(kf, qf[ks], s);
       }
-      float mt = MASKED;                      // scores (natural units) and the block's row maximum
+      float mt = kMasked;                      // scores (natural units) and the block's row maximum
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const int kl = kt * 32 + 8 * g + 4 * half;   // 4 consecutive keys: regs 4g .. 4g+3
@@ -412,9 +383,9 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 && DP <= 64) ? (FK == 32 ? 3 :
         }
       }
       mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
-      const float m_new = (mt > m_run + RESCALE_TAU) ? mt : m_run;
+      const float m_new = (mt > m_run + kRescaleTau) ? mt : m_run;
       if (__builtin_amdgcn_ballot_w64(m_new != m_run)) {   // rare after the first tiles (wave-uniform branch)
-        const float alpha = fast_exp2((m_run - m_new) * LOG2E);
+        const float alpha = fast_exp2((m_run - m_new) * kLog2e);
         l_run *= alpha;
         m_run = m_new;
 #pragma unroll
@@ -422,11 +393,11 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 && DP <= 64) ? (FK == 32 ? 3 :
 #pragma unroll
           for (int r = 0; r < 16; ++r) o[t2][r] *= alpha;
       }
-      const float nm = -m_run * LOG2E;
+      const float nm = -m_run * kLog2e;
       float ls = 0.f;
       auto soft = [&](auto r_c) {
         constexpr int r = decltype(r_c)::value;
-        float e = fast_exp2(fmaf(s[r], LOG2E, nm));
+        float e = fast_exp2(fmaf(s[r], kLog2e, nm));
         ls += e;
         if constexpr (DROP) e = mask_keep(e, lane_words_mask(cw, 2 * (16 * kt + r) + wsel));
         s[r] = e;
@@ -469,15 +440,15 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 && DP <= 64) ? (FK == 32 ? 3 :
   __syncthreads();
   float* myO = reinterpret_cast<float*>(smem) + wave * 32 * (DP + 1);
   // `any`: some key of the row is not masked.  With every key at -1e30 the running maximum is -1e30 too and the exponent
-  // fmaf(s, LOG2E, nm) is the rounding error of that product, up to 2^76 of either sign: P can be inf and O inf - inf
-  const bool any = m_run > 0.5f * MASKED;
+  // fmaf(s, kLog2e, nm) is the rounding error of that product, up to 2^76 of either sign: P can be inf and O inf - inf
+  const bool any = m_run > 0.5f * kMasked;
   const float inv = (any && l_run > 0.f) ? keep_scale / l_run : 0.f;
 #pragma unroll
   for (int t = 0; t < DT; ++t)
 #pragma unroll
     for (int r = 0; r < 16; ++r)   // (a row whose keys are all masked: zeros - its accumulators can hold inf / NaN, see `any`)
       myO[(lane & 31) * (DP + 1) + t * 32 + acc_row(r, lane)] = any ? o[t][r] * inv : 0.f;
-  if (half == 0 && myq < Tn && p.lse) p.lse[((int64_t)b * p.nh + h) * Tn + myq] = any ? fmaf(m_run, LOG2E, log2f(l_run)) : MASKED;  // log2 units
+  if (half == 0 && myq < Tn && p.lse) p.lse[((int64_t)b * p.nh + h) * Tn + myq] = any ? fmaf(m_run, kLog2e, log2f(l_run)) : kMasked;  // log2 units
   __syncthreads();
   T* O = reinterpret_cast<T*>(p.out) + (int64_t)b * Tn * p.ld_out + h * d;
   store_rows<T, DP>(myO, O, p.ld_out, q0 + wave * 32, Tn, d, lane);
@@ -564,7 +535,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnParams p) {
   const int myq = q0 + wave * 32 + (lane & 31);
   const int qrow = wave * 32 + (lane & 31);
   const float keep_scale = DROP ? p.keep_scale : 1.0f;
-  const float sc2 = p.scale * LOG2E;
+  const float sc2 = p.scale * kLog2e;
   const uint32_t* wbh = DROP ? p.words + ((int64_t)b * p.nh + h) * p.nqb * (int64_t)p.Tk : nullptr;
   const bool k_al = ((reinterpret_cast<uintptr_t>(K) & 15) == 0) && ((reinterpret_cast<uintptr_t>(V) & 15) == 0) &&
                     ((p.ld * (int64_t)sizeof(T)) % 16 == 0) && (d == DP);
@@ -606,7 +577,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnParams p) {
     tile_store<T, AK, DP>(rv, sV, tid);
     tile_store<T, DP, AK>(rkt, sKt, tid);
     if (bias) bias_store<T, AQ>(rb, sB, tid);
-    if (tid < AK) sKb[tid] = (k0 + tid < Tn) ? (kb ? kb[k0 + tid] * LOG2E : 0.f) : MASKED;
+    if (tid < AK) sKb[tid] = (k0 + tid < Tn) ? (kb ? kb[k0 + tid] * kLog2e : 0.f) : kMasked;
     __syncthreads();
     DQ_PREFETCH(t + 1 < ntile ? t + 1 : t)
 
@@ -633,7 +604,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnParams p) {
         float dsv[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          const float v = fmaf(s[kt][4 * g + e], sc2, fmaf(bb[e], LOG2E, sKb[kl + e]));
+          const float v = fmaf(s[kt][4 * g + e], sc2, fmaf(bb[e], kLog2e, sKb[kl + e]));
           const float pr = (myq < Tn) ? fast_exp2(v - my_lse) : 0.f;
           float dpv = dp[kt][4 * g + e];
           if (DROP) dpv = attn_word_keep(wbh, p.Tk, myq, k0 + kl + e) ? dpv * keep_scale : 0.f;
@@ -708,9 +679,9 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(AttnParams p) {
   const T* dOt = reinterpret_cast<const T*>(p.dot) + ((int64_t)b * p.nh + h) * DP * Tp;
   const T* bias = p.bias ? reinterpret_cast<const T*>(p.bias) + ((int64_t)b * p.nh + h) * Tn * p.bias_ld : nullptr;
   const int mykey = key0 + wave * 32 + (lane & 31);
-  const float my_kb = (mykey < Tn) ? (p.key_bias ? p.key_bias[(int64_t)b * Tp + mykey] * LOG2E : 0.f) : MASKED;
+  const float my_kb = (mykey < Tn) ? (p.key_bias ? p.key_bias[(int64_t)b * Tp + mykey] * kLog2e : 0.f) : kMasked;
   const float keep_scale = DROP ? p.keep_scale : 1.0f;
-  const float sc2 = p.scale * LOG2E;
+  const float sc2 = p.scale * kLog2e;
   const uint32_t* wbh = DROP ? p.words + ((int64_t)b * p.nh + h) * p.nqb * (int64_t)p.Tk : nullptr;
   const bool q_al = ((reinterpret_cast<uintptr_t>(Q) & 15) == 0) && ((p.ld * (int64_t)sizeof(T)) % 16 == 0) && (d == DP);
   const bool do_al = ((reinterpret_cast<uintptr_t>(dO) & 15) == 0) && ((p.ld_out * (int64_t)sizeof(T)) % 16 == 0) && (d == DP);
@@ -797,7 +768,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(AttnParams p) {
         const int qq = q0 + ql;
         float bv = 0.f;
         if (bias) bv = Elem<T>::load(reinterpret_cast<const T*>(sB + ql * BP) + wave * 32 + (lane & 31));
-        const float v = fmaf(s[qt][r], sc2, fmaf(bv, LOG2E, my_kb));
+        const float v = fmaf(s[qt][r], sc2, fmaf(bv, kLog2e, my_kb));
         const float pv = (qq < Tn) ? fast_exp2(v - sLse[ql]) : 0.f;
         float dpv = dp[qt][r];
         float pdrop = pv;
@@ -908,7 +879,7 @@ __global__ __launch_bounds__(256, OCC) void attn_bwd_fused_kernel(AttnParams p, 
   const int64_t ldq = (int64_t)p.nh * d;
   const int keyl = wave * 32 + (lane & 31);
   const int mykey = key0 + keyl;
-  const float my_kb = (mykey < Tn) ? (p.key_bias ? p.key_bias[(int64_t)b * Tp + mykey] : 0.f) : MASKED;   // natural units
+  const float my_kb = (mykey < Tn) ? (p.key_bias ? p.key_bias[(int64_t)b * Tp + mykey] : 0.f) : kMasked;   // natural units
   const bool add_kb = HAS_BIAS && p.key_bias != nullptr;   // (with a bias tensor its padding columns mask keys >= T)
   const float keep_scale = DROP ? p.keep_scale : 1.0f;
   // this lane's key column of the keep words: one dword per 32-query block
@@ -968,7 +939,7 @@ __global__ __launch_bounds__(256, OCC) void attn_bwd_fused_kernel(AttnParams p, 
     if (tid < FQ) {
       const int qq = q0 + tid;
       const int64_t rowid = ((int64_t)b * p.nh + h) * Tn + qq;
-      sLse[tid] = qq < Tn ? -p.lse[rowid] : MASKED;   // minus lse (log2 units); rows past T give P = exp2(-huge) = 0
+      sLse[tid] = qq < Tn ? -p.lse[rowid] : kMasked;   // minus lse (log2 units); rows past T give P = exp2(-huge) = 0
       sDelta[tid] = qq < Tn ? p.delta[rowid] : 0.f;
     }
     const uint32_t cw0 = rw0 >> (4 * half), cw1 = rw1 >> (4 * half);   // bit (8 (r / 4) + r % 4) = this lane's query of register r
@@ -1012,8 +983,7 @@ __global__ __launch_bounds__(256, OCC) void attn_bwd_fused_kernel(AttnParams p, 
         const float nl4[4] = {l4.x, l4.y, l4.z, l4.w}, del4[4] = {d4.x, d4.y, d4.z, d4.w};
         float bv4[4] = {my_kb, my_kb, my_kb, my_kb};
         if constexpr (HAS_BIAS) {   // the four queries' bias of this lane's key: one transpose read of the [q][key] tile
-          typedef __attribute__((address_space(3))) s16x4_t* lds_s4p;
-          const uint2 u = __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4p)(sB + (qb + trk) * PB + trc * 2)));
+          const uint2 u = tr64(sB + (qb + trk) * PB + trc * 2);
           bv4[0] = __uint_as_float(u.x << 16); bv4[1] = __uint_as_float(u.x & 0xffff0000u);
           bv4[2] = __uint_as_float(u.y << 16); bv4[3] = __uint_as_float(u.y & 0xffff0000u);
           if (add_kb) {
@@ -1026,7 +996,7 @@ __global__ __launch_bounds__(256, OCC) void attn_bwd_fused_kernel(AttnParams p, 
         for (int e = 0; e < 4; ++e) {
           const int r = 4 * g + e, ql = qb + e, qq = q0 + ql;
           const float v = fmaf(s[r], p.scale, bv4[e]);
-          const float pv = fast_exp2(fmaf(v, LOG2E, nl4[e]));
+          const float pv = fast_exp2(fmaf(v, kLog2e, nl4[e]));
           float pdrop = pv, ks = keep_scale;
           if (DROP) {
             const int m = __builtin_amdgcn_sbfe((int)cw, 8 * g + e, 1);   // 0 / -1
@@ -1241,14 +1211,8 @@ template <typename T, int DP> static size_t dkv_smem() {
 }
 
 template <typename KernelT>
-static int set_smem(KernelT kern, size_t bytes) {
-  if (bytes > 64 * 1024) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {
-      set_error("attention: cannot raise dynamic LDS to %zu bytes", bytes);
-      return PENEO_ERR_LAUNCH;
-    }
-  }
-  return PENEO_OK;
+static int set_smem(KernelT kern, size_t bytes, const char* who) {
+  return bytes > 64 * 1024 ? raise_dynamic_lds(kern, bytes, who) : PENEO_OK;
 }
 
 template <typename T, int DP, bool DROP>
@@ -1265,21 +1229,21 @@ static int launch_fwd_d(const AttnParams& p, hipStream_t st) {
         const bool narrow = (int64_t)grid.x * grid.y * grid.z > 512;
         if (narrow) {
           const size_t sh = fwd_smem<T, DP, 32>();
-          int rc = set_smem(attn_fwd_kernel<T, DP, DROP, true, 32>, sh);
+          int rc = set_smem(attn_fwd_kernel<T, DP, DROP, true, 32>, sh, "peneo_attn_fwd");
           if (rc) return rc;
           hipLaunchKernelGGL((attn_fwd_kernel<T, DP, DROP, true, 32>), grid, dim3(256), sh, st, p);
           return check_launch("peneo_attn_fwd");
         }
       }
       const size_t sh = fwd_smem<T, DP, AK>();
-      int rc = set_smem(attn_fwd_kernel<T, DP, DROP, true, AK>, sh);
+      int rc = set_smem(attn_fwd_kernel<T, DP, DROP, true, AK>, sh, "peneo_attn_fwd");
       if (rc) return rc;
       hipLaunchKernelGGL((attn_fwd_kernel<T, DP, DROP, true, AK>), grid, dim3(256), sh, st, p);
       return check_launch("peneo_attn_fwd");
     }
   }
   const size_t sh = fwd_smem<T, DP, AK>();
-  int rc = set_smem(attn_fwd_kernel<T, DP, DROP, false, AK>, sh);
+  int rc = set_smem(attn_fwd_kernel<T, DP, DROP, false, AK>, sh, "peneo_attn_fwd");
   if (rc) return rc;
   hipLaunchKernelGGL((attn_fwd_kernel<T, DP, DROP, false, AK>), grid, dim3(256), sh, st, p);
   return check_launch("peneo_attn_fwd");
@@ -1321,7 +1285,7 @@ static int launch_bwd_d(const AttnParams& p, float* dq_acc, hipStream_t st) {
           rc = launch_attn_bwd_pipe(p, st);
           if (rc <= 0) return rc;      // 0: dK, dV, the slab AND dQ are launched
           size_t sq = dqs_smem<DP>();
-          rc = set_smem(attn_dq_from_ds_kernel<DP>, sq);
+          rc = set_smem(attn_dq_from_ds_kernel<DP>, sq, "peneo_attn_bwd");
           if (rc) return rc;
           dim3 qgrid((p.T + AQ - 1) / AQ, p.nh, p.B);
           hipLaunchKernelGGL((attn_dq_from_ds_kernel<DP>), qgrid, dim3(256), sq, st, p);
@@ -1333,7 +1297,7 @@ static int launch_bwd_d(const AttnParams& p, float* dq_acc, hipStream_t st) {
       const int occ = DP <= 64 ? 2 : 1;        // workgroups per CU (256 registers at head dims above 64)
 #define PENEO_LAUNCH_FUSED(HB_, OCC_)                                                                        \
   {                                                                                                          \
-    rc = set_smem(attn_bwd_fused_kernel<DP, DROP, HB_, OCC_>, sf);                                           \
+    rc = set_smem(attn_bwd_fused_kernel<DP, DROP, HB_, OCC_>, sf, "peneo_attn_bwd");                         \
     if (rc) return rc;                                                                                       \
     hipLaunchKernelGGL((attn_bwd_fused_kernel<DP, DROP, HB_, OCC_>), fgrid, dim3(256), sf, st, p, dq_acc);    \
   }
@@ -1344,7 +1308,7 @@ static int launch_bwd_d(const AttnParams& p, float* dq_acc, hipStream_t st) {
       if (rc) return rc;
       if (dq_from_ds) {
         size_t sq = dqs_smem<DP>();
-        rc = set_smem(attn_dq_from_ds_kernel<DP>, sq);
+        rc = set_smem(attn_dq_from_ds_kernel<DP>, sq, "peneo_attn_bwd");
         if (rc) return rc;
         dim3 qgrid((p.T + AQ - 1) / AQ, p.nh, p.B);
         hipLaunchKernelGGL((attn_dq_from_ds_kernel<DP>), qgrid, dim3(256), sq, st, p);
@@ -1359,13 +1323,13 @@ static int launch_bwd_d(const AttnParams& p, float* dq_acc, hipStream_t st) {
   }
   dim3 grid((p.T + AQ - 1) / AQ, p.nh, p.B);
   size_t s1 = dq_smem<T, DP>();
-  rc = set_smem(attn_bwd_dq_kernel<T, DP, DROP>, s1);
+  rc = set_smem(attn_bwd_dq_kernel<T, DP, DROP>, s1, "peneo_attn_bwd");
   if (rc) return rc;
   hipLaunchKernelGGL((attn_bwd_dq_kernel<T, DP, DROP>), grid, dim3(256), s1, st, p);
   rc = check_launch("peneo_attn_bwd(dq)");
   if (rc) return rc;
   size_t s2 = dkv_smem<T, DP>();
-  rc = set_smem(attn_bwd_dkv_kernel<T, DP, DROP>, s2);
+  rc = set_smem(attn_bwd_dkv_kernel<T, DP, DROP>, s2, "peneo_attn_bwd");
   if (rc) return rc;
   hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, DP, DROP>), grid, dim3(256), s2, st, p);
   return check_launch("peneo_attn_bwd(dkv)");

@@ -33,6 +33,7 @@
 // another workgroup.
 #include "common.h"
 #include "attention.h"
+#include "attn_pipe.h"
 
 namespace peneo {
 namespace {
@@ -58,59 +59,9 @@ constexpr int O_QA = 0, O_DOA = 4096, O_QB = 8192, O_DOB = 9216, O_LSE = 10240, 
 constexpr int STG_PITCH = 80, STG_WAVE = 32 * STG_PITCH;
 constexpr int NBUF = 3;
 constexpr int LDS_BYTES = NBUF * BUF + 4 * STG_WAVE;
-constexpr float kLog2e = 1.4426950408889634f;
-constexpr float kMasked = -1.0e30f;
 
 __device__ float g_lse_pad2 = 1.0e30f;   // lse of query rows past T
 __device__ uint4 g_zero_line2[8];        // 128 zero bytes (device globals are zero-initialised)
-
-__device__ __forceinline__ int bitrev3(int x) { return ((x & 1) << 2) | (x & 2) | ((x >> 2) & 1); }
-__device__ __forceinline__ int qslot_swz(int row) { return bitrev3((row >> 1) & 7); }
-
-typedef short s16x4_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ uint2 tr64(const char* p) {
-  typedef __attribute__((address_space(3))) s16x4_t* lds_s4p;
-  return __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4p)p));
-}
-__device__ __forceinline__ Frag<bf16_t> tr_frag(const char* lo, const char* hi) {
-  const uint2 a = tr64(lo), b = tr64(hi);
-  Frag<bf16_t> f;
-  f.v = make_uint4(a.x, a.y, b.x, b.y);
-  return f;
-}
-// 64 lanes x 4 bytes: global (uniform base + lane offset) -> LDS (uniform base + 4 * lane)
-__device__ __forceinline__ void dma4_s(uint32_t voff_lane, const char* base_uniform, uint32_t lds_uniform) {
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff_lane), "s"(base_uniform), "s"(lds_uniform) : "memory");
-}
-// ... with a full per-lane pointer
-__device__ __forceinline__ void dma4_v(const char* ptr_lane, uint32_t lds_uniform) {
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(ptr_lane), "s"(lds_uniform) : "memory");
-}
-__device__ __forceinline__ uint32_t and_u(float x, int m) { return __float_as_uint(x) & (uint32_t)m; }
-// 8 bf16 of a key row, times `scale`, rounded to bf16 again (exact for a power of two)
-__device__ __forceinline__ uint4 scaled8(const bf16_t* p, float scale, bool ok) {
-  float f[8];
-  unpack16<bf16_t>(*reinterpret_cast<const uint4*>(p), f);
-  if (scale != 1.0f) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) f[e] *= scale;
-  }
-  const uint4 v = pack16<bf16_t>(f);
-  return ok ? v : make_uint4(0u, 0u, 0u, 0u);
-}
-// rows d = 16 m + 8 half .. + 7 of an accumulator tile [d rows (registers)][key or query (lane)], times mul, as 8 bf16: two register
-// groups and a v_permlane32_swap make 16 contiguous bytes per lane (run with every lane active)
-__device__ __forceinline__ uint4 acc_piece(const f32x16_t& a, int m, float mul) {
-  uint32_t ax = pack_bf16x2(a[8 * m + 0] * mul, a[8 * m + 1] * mul), ay = pack_bf16x2(a[8 * m + 2] * mul, a[8 * m + 3] * mul);
-  uint32_t bx = pack_bf16x2(a[8 * m + 4] * mul, a[8 * m + 5] * mul), by = pack_bf16x2(a[8 * m + 6] * mul, a[8 * m + 7] * mul);
-  const auto rx = __builtin_amdgcn_permlane32_swap(ax, bx, false, false);
-  const auto ry = __builtin_amdgcn_permlane32_swap(ay, by, false, false);
-  return make_uint4(rx[0], ry[0], rx[1], ry[1]);
-}
 
 // ================================================================================================
 // 1. delta
@@ -161,11 +112,7 @@ __global__ __launch_bounds__(256, 2) void attn2_bwd_pipe_kernel(Attn2BwdParams p
   const int Tn = p.T, Tp = p.Tp;
   // unit order: the key blocks of one (document, head) run on ONE XCD (they stream the same Q / dO rows through its L2)
   const int nkb = (Tn + WK - 1) / WK;
-  int u;
-  {
-    const int nwg = gridDim.x, L = blockIdx.x, q8 = nwg >> 3, r8 = nwg & 7, x = L & 7, i = L >> 3;
-    u = (x < r8 ? x * (q8 + 1) : r8 * (q8 + 1) + (x - r8) * q8) + i;
-  }
+  const int u = xcd_unit();
   const int kb = u % nkb, bh = u / nkb, h = bh % p.nh, b = bh / p.nh;
   const int key0 = kb * WK;
   const int keyl = wave * 32 + l31, mykey = key0 + keyl;
@@ -215,7 +162,7 @@ __global__ __launch_bounds__(256, 2) void attn2_bwd_pipe_kernel(Attn2BwdParams p
   const uint32_t ldq2 = (uint32_t)(p.ld_a * 2), ldo2 = (uint32_t)(p.ld_out_a * 2);
   const uint32_t ldb2 = (uint32_t)((wave == 2 ? p.ld_b : p.ld_out_b) * 2);       // (waves 2 and 3 only)
   const int qrow = 8 * wave + (lane >> 3);
-  const uint32_t qcol = (uint32_t)(((lane & 7) ^ qslot_swz(qrow)) << 4);
+  const uint32_t qcol = (uint32_t)(((lane & 7) ^ row128_slot_swz(qrow)) << 4);
   const int brow = lane >> 1;
   const uint32_t bcol = (uint32_t)(((lane & 1) ^ (brow >> 4)) << 4);
   // tiles are requested strictly in order: the uniform source pointers of the NEXT tile to request run along (scalar adds)
@@ -248,7 +195,7 @@ __global__ __launch_bounds__(256, 2) void attn2_bwd_pipe_kernel(Attn2BwdParams p
 
   // ---- LDS read addresses (lane constants relative to a buffer) ----
   // S / dP fragment of text k-step ks: row l31, slot (2 ks + half) ^ swz = base ^ (ks << 5); of the layout k-step: aSb
-  const int aS0 = l31 * 128 + ((half ^ qslot_swz(l31)) << 4);
+  const int aS0 = l31 * 128 + ((half ^ row128_slot_swz(l31)) << 4);
   const int aSb = l31 * 32 + ((half ^ (l31 >> 4)) << 4);
   const int li = lane & 15, lj = (lane >> 4) & 1;
   int aT[2][2];                                      // transpose reads of the Q_a / dO_a tile: [d tile][rows +0 / +8]; + 2048 kk
@@ -259,7 +206,7 @@ __global__ __launch_bounds__(256, 2) void attn2_bwd_pipe_kernel(Attn2BwdParams p
 #pragma unroll
     for (int t2 = 0; t2 < 2; ++t2) {
       const int slot = 4 * t2 + 2 * lj + ((li & 3) >> 1);
-      aT[t2][w8] = row * 128 + ((slot ^ qslot_swz(row)) << 4) + ((li & 1) << 3);
+      aT[t2][w8] = row * 128 + ((slot ^ row128_slot_swz(row)) << 4) + ((li & 1) << 3);
     }
     aTb[w8] = (row ^ (8 * lj)) * 32 + ((li & 3) << 3);   // (lj = 1: the pad rows' groups read the other eight query rows)
   }
@@ -445,11 +392,7 @@ __global__ __launch_bounds__(256, 2) void attn2_dq_pipe_kernel(Attn2BwdParams p)
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int Tn = p.T, Tp = p.Tp;
   const int nqb = (Tn + 127) / 128;
-  int u;
-  {
-    const int nwg = gridDim.x, L = blockIdx.x, q8 = nwg >> 3, r8 = nwg & 7, x = L & 7, i = L >> 3;
-    u = (x < r8 ? x * (q8 + 1) : r8 * (q8 + 1) + (x - r8) * q8) + i;
-  }
+  const int u = xcd_unit();
   const int qb = u % nqb, bh = u / nqb, h = bh % p.nh, b = bh / p.nh;
   const int q0 = qb * 128, myq = q0 + wave * 32 + l31;
   const int64_t row0 = (int64_t)b * Tn;
@@ -464,7 +407,7 @@ __global__ __launch_bounds__(256, 2) void attn2_dq_pipe_kernel(Attn2BwdParams p)
   const int scl = Tp * 2 - 16;                                   // (a query block may pass the padded row end: clamp; those rows are not stored)
   const uint32_t sc0 = (uint32_t)min(q0 * 2 + (((lane & 15) ^ ((srow0 & 3) << 2)) << 4), scl);
   const uint32_t sc1 = (uint32_t)min(q0 * 2 + (((lane & 15) ^ (((srow0 + 4) & 3) << 2)) << 4), scl);
-  const uint32_t kcol = (uint32_t)(((lane & 7) ^ qslot_swz(krow)) << 4);
+  const uint32_t kcol = (uint32_t)(((lane & 7) ^ row128_slot_swz(krow)) << 4);
   const uint32_t bcol = (uint32_t)(((lane & 1) ^ (brow >> 4)) << 4);
   const char* ns = reinterpret_cast<const char*>(DS);
   const char* nk = reinterpret_cast<const char*>(Ka);
@@ -498,7 +441,7 @@ __global__ __launch_bounds__(256, 2) void attn2_dq_pipe_kernel(Attn2BwdParams p)
     aA[w4] = DQ_O_S + row * 256 + (((4 * wave + 2 * lj + ((li & 3) >> 1)) ^ ((row & 3) << 2)) << 4) + ((li & 1) << 3);
 #pragma unroll
     for (int t2 = 0; t2 < 2; ++t2)
-      aK[t2][w4] = DQ_O_KA + row * 128 + (((4 * t2 + 2 * lj + ((li & 3) >> 1)) ^ qslot_swz(row)) << 4) + ((li & 1) << 3);
+      aK[t2][w4] = DQ_O_KA + row * 128 + (((4 * t2 + 2 * lj + ((li & 3) >> 1)) ^ row128_slot_swz(row)) << 4) + ((li & 1) << 3);
     aKb[w4] = (row ^ (4 * lj)) * 32 + ((li & 3) << 3);           // (lj = 1, the d rows that do not exist: the other four key rows); (^ (kk << 4)) + 512 kk
   }
   f32x16_t acc[2], accb;

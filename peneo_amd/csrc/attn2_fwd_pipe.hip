@@ -29,6 +29,7 @@
 //     pre-dropout log-sum-exp), both value streams under the same mask, 1 / (1 - p) once on the accumulators.
 // Nothing here waits on another workgroup.
 #include "common.h"
+#include "attn_pipe.h"
 
 namespace peneo {
 namespace {
@@ -50,44 +51,6 @@ constexpr int WQ = 128;           // queries per workgroup (4 waves x 32)
 constexpr int O_KA = 0, O_VA = 4096, O_KB = 8192, O_VB = 9216, O_BIAS = 10240, O_WORDS = 10496;
 constexpr int NBUF = 3;
 constexpr int buf_bytes(bool drop) { return drop ? O_WORDS + 1024 : O_WORDS; }
-constexpr float kLog2e = 1.4426950408889634f;
-constexpr float kMasked = -1.0e30f;
-constexpr float kRescaleTau = 4.0f;   // (attention.hip: RESCALE_TAU)
-
-__device__ __forceinline__ int bitrev3(int x) { return ((x & 1) << 2) | (x & 2) | ((x >> 2) & 1); }
-__device__ __forceinline__ int kslot_swz(int row) { return bitrev3((row >> 1) & 7); }
-
-typedef short s16x4_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ uint2 tr64(const char* p) {
-  typedef __attribute__((address_space(3))) s16x4_t* lds_s4p;
-  return __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4p)p));
-}
-__device__ __forceinline__ void dma4_s(uint32_t voff_lane, const char* base_uniform, uint32_t lds_uniform) {
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff_lane), "s"(base_uniform), "s"(lds_uniform) : "memory");
-}
-// x where the lane's bit of the 64-bit mask is set, else 0 (attention.hip: mask_keep; the s_nop pads the VALU-written-SGPR hazard)
-__device__ __forceinline__ float mask_keep(float x, uint64_t m) {
-  float r;
-  asm("s_nop 1\n\tv_cndmask_b32_e64 %0, 0, %1, %2" : "=v"(r) : "v"(x), "s"(m));
-  return r;
-}
-__device__ __forceinline__ uint64_t lane_words_mask(uint32_t w, int word /* even, compile-time */) {
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)w, word), hi = (uint32_t)__builtin_amdgcn_readlane((int)w, word + 1);
-  return (uint64_t)lo | ((uint64_t)hi << 32);
-}
-// 8 bf16 of a query row, times `scale`, rounded to bf16 again (peneo_head_concat's arithmetic)
-__device__ __forceinline__ uint4 scaled_q(const bf16_t* p, float scale, bool ok) {
-  float f[8];
-  unpack16<bf16_t>(*reinterpret_cast<const uint4*>(p), f);
-  if (scale != 1.0f) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) f[e] *= scale;
-  }
-  const uint4 v = pack16<bf16_t>(f);
-  return ok ? v : make_uint4(0u, 0u, 0u, 0u);
-}
 
 template <bool DROP>
 __global__ __launch_bounds__(256, 2) void attn2_fwd_pipe_kernel(Attn2Params p) {
@@ -99,11 +62,7 @@ __global__ __launch_bounds__(256, 2) void attn2_fwd_pipe_kernel(Attn2Params p) {
   const int Tn = p.T;
   // unit order: the query blocks of one (document, head) run on ONE XCD (they stream the same K / V rows through its L2)
   const int nqb = (Tn + WQ - 1) / WQ;
-  int u;
-  {
-    const int nwg = gridDim.x, L = blockIdx.x, q8 = nwg >> 3, r8 = nwg & 7, x = L & 7, i = L >> 3;
-    u = (x < r8 ? x * (q8 + 1) : r8 * (q8 + 1) + (x - r8) * q8) + i;
-  }
+  const int u = xcd_unit();
   const int qb = u % nqb, bh = u / nqb, h = bh % p.nh, b = bh / p.nh;
   const int q0 = qb * WQ;
   const int myq = q0 + wave * 32 + l31;
@@ -123,8 +82,8 @@ __global__ __launch_bounds__(256, 2) void attn2_fwd_pipe_kernel(Attn2Params p) {
     const bool ok = myq < Tn;
     const T* qr = Qa + (int64_t)(ok ? myq : 0) * p.ld_a + 8 * half;
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) qf[ks].v = scaled_q(qr + 16 * ks, p.scale_a, ok);
-    qf[4].v = scaled_q(Qb + (int64_t)(ok ? myq : 0) * p.ld_b + 8 * half, p.scale_b, ok);
+    for (int ks = 0; ks < 4; ++ks) qf[ks].v = scaled8(qr + 16 * ks, p.scale_a, ok);
+    qf[4].v = scaled8(Qb + (int64_t)(ok ? myq : 0) * p.ld_b + 8 * half, p.scale_b, ok);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // from here on the vm counter holds the DMA pieces only
 #pragma unroll
@@ -135,7 +94,7 @@ __global__ __launch_bounds__(256, 2) void attn2_fwd_pipe_kernel(Attn2Params p) {
   const uint32_t lds0 = lds_addr(smem);
   const uint32_t lda2 = (uint32_t)(p.ld_a * 2), ldb2 = (uint32_t)(p.ld_b * 2);
   const int krow = 8 * wave + (lane >> 3);
-  const uint32_t kcol = (uint32_t)(((lane & 7) ^ kslot_swz(krow)) << 4);
+  const uint32_t kcol = (uint32_t)(((lane & 7) ^ row128_slot_swz(krow)) << 4);
   const int brow = lane >> 1;
   const uint32_t bcol = (uint32_t)(((lane & 1) ^ (brow >> 4)) << 4);
   const char* nka = reinterpret_cast<const char*>(Ka);
@@ -159,7 +118,7 @@ __global__ __launch_bounds__(256, 2) void attn2_fwd_pipe_kernel(Attn2Params p) {
   };
 
   // ---- LDS read addresses (lane constants relative to a buffer) ----
-  const int aS0 = l31 * 128 + ((half ^ kslot_swz(l31)) << 4);           // K_a fragment of k-step ks: ^ (ks << 5)
+  const int aS0 = l31 * 128 + ((half ^ row128_slot_swz(l31)) << 4);           // K_a fragment of k-step ks: ^ (ks << 5)
   const int aSb = O_KB + l31 * 32 + ((half ^ (l31 >> 4)) << 4);          // K_b fragment
   const int li = lane & 15, lj = (lane >> 4) & 1;
   int aT[2][2];                                                          // transpose reads of the V_a tile: [d tile][rows +0 / +8]; + 2048 kh
@@ -169,7 +128,7 @@ __global__ __launch_bounds__(256, 2) void attn2_fwd_pipe_kernel(Attn2Params p) {
     for (int w8 = 0; w8 < 2; ++w8) {
       const int row = 4 * half + (li >> 2) + 8 * w8;
       const int slot = 4 * t2 + 2 * lj + ((li & 3) >> 1);
-      aT[t2][w8] = row * 128 + ((slot ^ kslot_swz(row)) << 4) + ((li & 1) << 3);
+      aT[t2][w8] = row * 128 + ((slot ^ row128_slot_swz(row)) << 4) + ((li & 1) << 3);
     }
   int aTb[2];                                                            // of the V_b tile: [rows +0 / +8]; (^ (kh << 4)) + 512 kh
 #pragma unroll
@@ -318,6 +277,8 @@ __global__ __launch_bounds__(256, 2) void attn2_fwd_pipe_kernel(Attn2Params p) {
   // (a row whose keys are all masked: zeros - with the running maximum at -1e30 its P can be inf and its accumulators inf - inf,
   // attention.hip: `any`)
   auto nz = [&](float x) { return any ? x * inv : 0.f; };
+  // acc_piece (attn_pipe.h) with nz in place of the multiply; written out here: through acc_piece the compiler schedules this
+  // epilogue differently
   auto piece = [&](const f32x16_t& a, int m) {       // d rows 16 m + 8 half .. + 7 of an accumulator tile, as 8 bf16
     uint32_t ax = pack_bf16x2(nz(a[8 * m + 0]), nz(a[8 * m + 1])), ay = pack_bf16x2(nz(a[8 * m + 2]), nz(a[8 * m + 3]));
     uint32_t bx = pack_bf16x2(nz(a[8 * m + 4]), nz(a[8 * m + 5])), by = pack_bf16x2(nz(a[8 * m + 6]), nz(a[8 * m + 7]));

@@ -22,9 +22,9 @@
 //   * dS^T of a tile goes through a per-wave LDS patch (no barrier: the wave that writes it reads it back) and is stored at the top
 //     of the NEXT iteration, so the top-of-tile s_waitcnt vmcnt(0) finds stores that have had a whole tile to drain;
 //   * dK / dV leave as 16-byte row pieces straight from the accumulator layout (v_permlane32_swap pairs), no LDS round trip.
-#include <cstdlib>
 #include "common.h"
 #include "attention.h"
+#include "attn_pipe.h"
 
 namespace peneo {
 namespace {
@@ -40,37 +40,8 @@ constexpr int STG_PITCH = 80, STG_WAVE = 32 * STG_PITCH;
 // better in the step: the launch is bound by the CU's global -> LDS fill and by instruction issue, not by workgroups per CU.
 constexpr int NBUF = 3;
 constexpr int LDS_BYTES = NBUF * BUF + 4 * STG_WAVE;
-constexpr float kLog2e = 1.4426950408889634f;
 
 __device__ float g_lse_pad = 1.0e30f;   // lse of query rows past T
-
-__device__ __forceinline__ int bitrev3(int x) { return ((x & 1) << 2) | (x & 2) | ((x >> 2) & 1); }
-__device__ __forceinline__ int qslot_swz(int row) { return bitrev3((row >> 1) & 7); }
-
-typedef short s16x4_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ uint2 tr64(const char* p) {
-  typedef __attribute__((address_space(3))) s16x4_t* lds_s4p;
-  return __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4p)p));
-}
-__device__ __forceinline__ Frag<bf16_t> tr_frag(const char* lo, const char* hi) {
-  const uint2 a = tr64(lo), b = tr64(hi);
-  Frag<bf16_t> f;
-  f.v = make_uint4(a.x, a.y, b.x, b.y);
-  return f;
-}
-// 64 lanes x 4 bytes: global (uniform base + lane offset) -> LDS (uniform base + 4 * lane)
-__device__ __forceinline__ void dma4_s(uint32_t voff_lane, const char* base_uniform, uint32_t lds_uniform) {
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff_lane), "s"(base_uniform), "s"(lds_uniform) : "memory");
-}
-// ... with a full per-lane pointer
-__device__ __forceinline__ void dma4_v(const char* ptr_lane, uint32_t lds_uniform) {
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(ptr_lane), "s"(lds_uniform) : "memory");
-}
-__device__ __forceinline__ uint32_t and_u(float x, int m) { return __float_as_uint(x) & (uint32_t)m; }
 
 template <bool DROP>
 __global__ __launch_bounds__(256, 2) void attn_bwd_pipe_kernel(AttnParams p) {
@@ -81,11 +52,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_pipe_kernel(AttnParams p) {
   const int Tn = p.T, Tp = p.Tp;
   // unit order: the key blocks of one (document, head) run on ONE XCD (they stream the same Q / dO rows through its L2)
   const int nkb = (Tn + WK - 1) / WK;
-  int u;
-  {
-    const int nwg = gridDim.x, L = blockIdx.x, q8 = nwg >> 3, r8 = nwg & 7, x = L & 7, i = L >> 3;
-    u = (x < r8 ? x * (q8 + 1) : r8 * (q8 + 1) + (x - r8) * q8) + i;
-  }
+  const int u = xcd_unit();
   const int kb = u % nkb, bh = u / nkb, h = bh % p.nh, b = bh / p.nh;
   const int key0 = kb * WK;
   const int keyl = wave * 32 + l31, mykey = key0 + keyl;
@@ -130,7 +97,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_pipe_kernel(AttnParams p) {
   auto piece_offsets = [&](int lim, uint32_t& o0, uint32_t& o1, uint32_t& o2, uint32_t& o3) {
     const int bcl = (int)p.bias_ld * 2 - 16;                             // (a key block may pass the padded row end: clamp)
     const int qrow = 8 * wave + (lane >> 3);
-    const uint32_t qcol = (uint32_t)(((lane & 7) ^ qslot_swz(qrow)) << 4);
+    const uint32_t qcol = (uint32_t)(((lane & 7) ^ row128_slot_swz(qrow)) << 4);
     const int brow0 = 8 * wave + (lane >> 4);
     o0 = (uint32_t)min(qrow, lim) * ldq2 + qcol;
     o1 = (uint32_t)min(qrow, lim) * ldo2 + qcol;
@@ -171,7 +138,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_pipe_kernel(AttnParams p) {
 
   // ---- LDS read addresses (lane constants relative to a buffer) ----
   // S / dP fragment of k-step ks: row l31, slot (2 ks + half) ^ swz = base ^ (ks << 5)
-  const int aS0 = l31 * 128 + ((half ^ qslot_swz(l31)) << 4);
+  const int aS0 = l31 * 128 + ((half ^ row128_slot_swz(l31)) << 4);
   const int li = lane & 15, lj = (lane >> 4) & 1;
   int aT[2][2];                                      // transpose reads of the Q / dO tile: [d tile][rows +0 / +8]; + 2048 kk
 #pragma unroll
@@ -180,7 +147,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_pipe_kernel(AttnParams p) {
     for (int w8 = 0; w8 < 2; ++w8) {
       const int row = 4 * half + (li >> 2) + 8 * w8;
       const int slot = 4 * t2 + 2 * lj + ((li & 3) >> 1);
-      aT[t2][w8] = row * 128 + ((slot ^ qslot_swz(row)) << 4) + ((li & 1) << 3);
+      aT[t2][w8] = row * 128 + ((slot ^ row128_slot_swz(row)) << 4) + ((li & 1) << 3);
     }
   const int aB = O_BIAS + (4 * half + (li >> 2)) * 256 + (((4 * wave + 2 * lj + ((li & 3) >> 1)) ^ ((li >> 2) << 2)) << 4) + ((li & 1) << 3);
   const int aW = attn_kslot(keyl) * 4;
@@ -323,13 +290,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_pipe_kernel(AttnParams p) {
       for (int t2 = 0; t2 < 2; ++t2) {
         const f32x16_t& a = which == 0 ? dk[t2] : dv[t2];
 #pragma unroll
-        for (int m = 0; m < 2; ++m) {
-          uint32_t ax = pack_bf16x2(a[8 * m + 0] * mul, a[8 * m + 1] * mul), ay = pack_bf16x2(a[8 * m + 2] * mul, a[8 * m + 3] * mul);
-          uint32_t bx = pack_bf16x2(a[8 * m + 4] * mul, a[8 * m + 5] * mul), by = pack_bf16x2(a[8 * m + 6] * mul, a[8 * m + 7] * mul);
-          const auto rx = __builtin_amdgcn_permlane32_swap(ax, bx, false, false);
-          const auto ry = __builtin_amdgcn_permlane32_swap(ay, by, false, false);
-          *reinterpret_cast<uint4*>(dst + 32 * t2 + 16 * m + 8 * half) = make_uint4(rx[0], ry[0], rx[1], ry[1]);
-        }
+        for (int m = 0; m < 2; ++m) *reinterpret_cast<uint4*>(dst + 32 * t2 + 16 * m + 8 * half) = acc_piece(a, m, mul);
       }
     }
   }
@@ -355,11 +316,7 @@ __global__ __launch_bounds__(256, 2) void attn_dq_pipe_kernel(AttnParams p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int Tn = p.T, Tp = p.Tp;
   const int nqb = (Tn + 127) / 128;
-  int u;
-  {
-    const int nwg = gridDim.x, L = blockIdx.x, q8 = nwg >> 3, r8 = nwg & 7, x = L & 7, i = L >> 3;
-    u = (x < r8 ? x * (q8 + 1) : r8 * (q8 + 1) + (x - r8) * q8) + i;
-  }
+  const int u = xcd_unit();
   const int qb = u % nqb, bh = u / nqb, h = bh % p.nh, b = bh / p.nh;
   const int q0 = qb * 128, myq = q0 + wave * 32 + l31;
   const T* DS = reinterpret_cast<const T*>(p.ds_out) + (int64_t)bh * Tn * (int64_t)Tp;
@@ -372,7 +329,7 @@ __global__ __launch_bounds__(256, 2) void attn_dq_pipe_kernel(AttnParams p) {
   const int scl = Tp * 2 - 16;                                   // (a query block may pass the padded row end: clamp; those rows are not stored)
   const uint32_t sc0 = (uint32_t)min(q0 * 2 + (((lane & 15) ^ ((srow0 & 3) << 2)) << 4), scl);
   const uint32_t sc1 = (uint32_t)min(q0 * 2 + (((lane & 15) ^ (((srow0 + 4) & 3) << 2)) << 4), scl);
-  const uint32_t kcol = (uint32_t)(((lane & 7) ^ qslot_swz(krow)) << 4);
+  const uint32_t kcol = (uint32_t)(((lane & 7) ^ row128_slot_swz(krow)) << 4);
   const char* ns = reinterpret_cast<const char*>(DS);
   const char* nk = reinterpret_cast<const char*>(K);
   int nk0 = 0;
@@ -399,7 +356,7 @@ __global__ __launch_bounds__(256, 2) void attn_dq_pipe_kernel(AttnParams p) {
     aA[w4] = DQ_O_S + row * 256 + (((4 * wave + 2 * lj + ((li & 3) >> 1)) ^ ((row & 3) << 2)) << 4) + ((li & 1) << 3);
 #pragma unroll
     for (int t2 = 0; t2 < 2; ++t2)
-      aK[t2][w4] = DQ_O_K + row * 128 + (((4 * t2 + 2 * lj + ((li & 3) >> 1)) ^ qslot_swz(row)) << 4) + ((li & 1) << 3);
+      aK[t2][w4] = DQ_O_K + row * 128 + (((4 * t2 + 2 * lj + ((li & 3) >> 1)) ^ row128_slot_swz(row)) << 4) + ((li & 1) << 3);
   }
   f32x16_t acc[2];
 #pragma unroll
@@ -441,21 +398,14 @@ __global__ __launch_bounds__(256, 2) void attn_dq_pipe_kernel(AttnParams p) {
 #pragma unroll
     for (int t2 = 0; t2 < 2; ++t2)
 #pragma unroll
-      for (int m = 0; m < 2; ++m) {
-        const f32x16_t& a = acc[t2];
-        uint32_t ax = pack_bf16x2(a[8 * m + 0] * p.scale, a[8 * m + 1] * p.scale), ay = pack_bf16x2(a[8 * m + 2] * p.scale, a[8 * m + 3] * p.scale);
-        uint32_t bx = pack_bf16x2(a[8 * m + 4] * p.scale, a[8 * m + 5] * p.scale), by = pack_bf16x2(a[8 * m + 6] * p.scale, a[8 * m + 7] * p.scale);
-        const auto rx = __builtin_amdgcn_permlane32_swap(ax, bx, false, false);
-        const auto ry = __builtin_amdgcn_permlane32_swap(ay, by, false, false);
-        *reinterpret_cast<uint4*>(dst + 32 * t2 + 16 * m + 8 * half) = make_uint4(rx[0], ry[0], rx[1], ry[1]);
-      }
+      for (int m = 0; m < 2; ++m) *reinterpret_cast<uint4*>(dst + 32 * t2 + 16 * m + 8 * half) = acc_piece(acc[t2], m, p.scale);
   }
 }
 
 }  // namespace
 
 bool attn_bwd_pipe_supported(const AttnParams& p) {
-  static const bool on = [] { const char* e = getenv("PENEO_ATTN_BWD_PIPE"); return !e || atoi(e) != 0; }();
+  static const bool on = env_switch_on("PENEO_ATTN_BWD_PIPE");
   auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
   return on && p.d == 64 && p.bias != nullptr && p.key_bias == nullptr && p.ds_out != nullptr && p.g_bias == nullptr &&
          al16(p.q) && al16(p.k) && al16(p.v) && al16(p.d_out) && al16(p.dk) && al16(p.dv) && al16(p.bias) && al16(p.ds_out) &&
@@ -466,17 +416,14 @@ bool attn_bwd_pipe_supported(const AttnParams& p) {
 int launch_attn_bwd_pipe(const AttnParams& p, hipStream_t st) {
   const dim3 grid((unsigned)((int64_t)((p.T + WK - 1) / WK) * p.nh * p.B));
   auto go = [&](auto kern, int lds) -> int {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
-      set_error("peneo_attn_bwd: cannot raise dynamic LDS to %d bytes", lds);
-      return PENEO_ERR_LAUNCH;
-    }
+    if (raise_dynamic_lds(kern, lds, "peneo_attn_bwd") != PENEO_OK) return PENEO_ERR_LAUNCH;
     hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, p);
     return check_launch("peneo_attn_bwd(pipe)");
   };
   int rc = p.drop_p > 0.f ? go(attn_bwd_pipe_kernel<true>, LDS_BYTES) : go(attn_bwd_pipe_kernel<false>, LDS_BYTES);
   if (rc) return rc;
   // dQ from the slab just written
-  static const bool dq_pipe = [] { const char* e = getenv("PENEO_ATTN_DQ_PIPE"); return !e || atoi(e) != 0; }();
+  static const bool dq_pipe = env_switch_on("PENEO_ATTN_DQ_PIPE");
   if (!dq_pipe || ((reinterpret_cast<uintptr_t>(p.dq) & 15) != 0)) return 1;   // 1: the caller launches attn_dq_from_ds_kernel
   const dim3 qgrid((unsigned)((int64_t)((p.T + 127) / 128) * p.nh * p.B));
   hipLaunchKernelGGL(attn_dq_pipe_kernel, qgrid, dim3(256), 3 * DQ_BUF, st, p);

@@ -12,9 +12,9 @@
 //   * keys past T: K / V rows are clamped to T - 1 and the ragged last tile masks its scores itself (round 6: one wave-uniform branch
 //     per launch; until then the kernel relied on -1e30 in the bias tensor's padding columns, which peneo_attn_fwd does not promise);
 //   * O rows leave as 16-byte pieces straight from the accumulator layout (v_permlane32_swap pairs), no LDS round trip.
-#include <cstdlib>
 #include "common.h"
 #include "attention.h"
+#include "attn_pipe.h"
 
 namespace peneo {
 namespace {
@@ -25,33 +25,6 @@ constexpr int WQ = 128;    // queries per workgroup (4 waves x 32)
 constexpr int O_K = 0, O_V = 4096, O_BIAS = 8192, O_WORDS = 16384, BUF = 17408;
 constexpr int NBUF = 3;
 constexpr int LDS_BYTES = NBUF * BUF;
-constexpr float kLog2e = 1.4426950408889634f;
-constexpr float kMasked = -1.0e30f;
-constexpr float kRescaleTau = 4.0f;   // (attention.hip: RESCALE_TAU)
-
-__device__ __forceinline__ int bitrev3(int x) { return ((x & 1) << 2) | (x & 2) | ((x >> 2) & 1); }
-__device__ __forceinline__ int kslot_swz(int row) { return bitrev3((row >> 1) & 7); }
-
-typedef short s16x4_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ uint2 tr64(const char* p) {
-  typedef __attribute__((address_space(3))) s16x4_t* lds_s4p;
-  return __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4p)p));
-}
-__device__ __forceinline__ void dma4_s(uint32_t voff_lane, const char* base_uniform, uint32_t lds_uniform) {
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff_lane), "s"(base_uniform), "s"(lds_uniform) : "memory");
-}
-// x where the lane's bit of the 64-bit mask is set, else 0 (attention.hip: mask_keep; the s_nop pads the VALU-written-SGPR hazard)
-__device__ __forceinline__ float mask_keep(float x, uint64_t m) {
-  float r;
-  asm("s_nop 1\n\tv_cndmask_b32_e64 %0, 0, %1, %2" : "=v"(r) : "v"(x), "s"(m));
-  return r;
-}
-__device__ __forceinline__ uint64_t lane_words_mask(uint32_t w, int word /* even, compile-time */) {
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)w, word), hi = (uint32_t)__builtin_amdgcn_readlane((int)w, word + 1);
-  return (uint64_t)lo | ((uint64_t)hi << 32);
-}
 
 template <bool DROP>
 __global__ __launch_bounds__(256, 2) void attn_fwd_pipe_kernel(AttnParams p) {
@@ -62,11 +35,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_pipe_kernel(AttnParams p) {
   const int Tn = p.T;
   // unit order: the query blocks of one (document, head) run on ONE XCD (they stream the same K / V rows through its L2)
   const int nqb = (Tn + WQ - 1) / WQ;
-  int u;
-  {
-    const int nwg = gridDim.x, L = blockIdx.x, q8 = nwg >> 3, r8 = nwg & 7, x = L & 7, i = L >> 3;
-    u = (x < r8 ? x * (q8 + 1) : r8 * (q8 + 1) + (x - r8) * q8) + i;
-  }
+  const int u = xcd_unit();
   const int qb = u % nqb, bh = u / nqb, h = bh % p.nh, b = bh / p.nh;
   const int q0 = qb * WQ;
   const int myq = q0 + wave * 32 + l31;
@@ -97,7 +66,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_pipe_kernel(AttnParams p) {
   const uint32_t lds0 = lds_addr(smem);
   const uint32_t ldk2 = (uint32_t)(p.ld * 2), ldb2 = (uint32_t)(p.bias_ld * 2);
   const int krow = 8 * wave + (lane >> 3);
-  const uint32_t kcol = (uint32_t)(((lane & 7) ^ kslot_swz(krow)) << 4);
+  const uint32_t kcol = (uint32_t)(((lane & 7) ^ row128_slot_swz(krow)) << 4);
   uint32_t bo0, bo1;                                 // bias pieces: row = 32 wave + 16 j + lane / 4, slot lane & 3 (source slot permuted)
   {
     const int r0 = 32 * wave + (lane >> 2), r1 = r0 + 16;
@@ -123,7 +92,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_pipe_kernel(AttnParams p) {
   };
 
   // ---- LDS read addresses (lane constants relative to a buffer) ----
-  const int aS0 = l31 * 128 + ((half ^ kslot_swz(l31)) << 4);           // K fragment of k-step ks: ^ (ks << 5)
+  const int aS0 = l31 * 128 + ((half ^ row128_slot_swz(l31)) << 4);           // K fragment of k-step ks: ^ (ks << 5)
   const int li = lane & 15, lj = (lane >> 4) & 1;
   int aT[2][2];                                                          // transpose reads of the V tile: [d tile][rows +0 / +8]; + 2048 kk
 #pragma unroll
@@ -132,7 +101,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_pipe_kernel(AttnParams p) {
     for (int w8 = 0; w8 < 2; ++w8) {
       const int row = 4 * half + (li >> 2) + 8 * w8;
       const int slot = 4 * t2 + 2 * lj + ((li & 3) >> 1);
-      aT[t2][w8] = row * 128 + ((slot ^ kslot_swz(row)) << 4) + ((li & 1) << 3);
+      aT[t2][w8] = row * 128 + ((slot ^ row128_slot_swz(row)) << 4) + ((li & 1) << 3);
     }
   const int qrow = wave * 32 + l31;
   const int aB0 = O_BIAS + qrow * 64 + 8 * half;                         // + ((g ^ swz) << 4)
@@ -266,21 +235,14 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_pipe_kernel(AttnParams p) {
 #pragma unroll
     for (int t2 = 0; t2 < 2; ++t2)
 #pragma unroll
-      for (int m = 0; m < 2; ++m) {
-        const f32x16_t& a = o[t2];
-        uint32_t ax = pack_bf16x2(a[8 * m + 0] * inv, a[8 * m + 1] * inv), ay = pack_bf16x2(a[8 * m + 2] * inv, a[8 * m + 3] * inv);
-        uint32_t bx = pack_bf16x2(a[8 * m + 4] * inv, a[8 * m + 5] * inv), by = pack_bf16x2(a[8 * m + 6] * inv, a[8 * m + 7] * inv);
-        const auto rx = __builtin_amdgcn_permlane32_swap(ax, bx, false, false);
-        const auto ry = __builtin_amdgcn_permlane32_swap(ay, by, false, false);
-        *reinterpret_cast<uint4*>(dst + 32 * t2 + 16 * m + 8 * half) = make_uint4(rx[0], ry[0], rx[1], ry[1]);
-      }
+      for (int m = 0; m < 2; ++m) *reinterpret_cast<uint4*>(dst + 32 * t2 + 16 * m + 8 * half) = acc_piece(o[t2], m, inv);
   }
 }
 
 }  // namespace
 
 bool attn_fwd_pipe_supported(const AttnParams& p) {
-  static const bool on = [] { const char* e = getenv("PENEO_ATTN_FWD_PIPE"); return !e || atoi(e) != 0; }();
+  static const bool on = env_switch_on("PENEO_ATTN_FWD_PIPE");
   auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
   return on && p.d == 64 && p.bias != nullptr && p.key_bias == nullptr && p.vt == nullptr && p.v != nullptr &&
          al16(p.q) && al16(p.k) && al16(p.v) && al16(p.out) && al16(p.bias) &&
@@ -292,10 +254,7 @@ bool attn_fwd_pipe_supported(const AttnParams& p) {
 int launch_attn_fwd_pipe(const AttnParams& p, hipStream_t st) {
   const dim3 grid((unsigned)((int64_t)((p.T + WQ - 1) / WQ) * p.nh * p.B));
   auto go = [&](auto kern) -> int {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) != hipSuccess) {
-      set_error("peneo_attn_fwd: cannot raise dynamic LDS to %d bytes", LDS_BYTES);
-      return PENEO_ERR_LAUNCH;
-    }
+    if (raise_dynamic_lds(kern, LDS_BYTES, "peneo_attn_fwd") != PENEO_OK) return PENEO_ERR_LAUNCH;
     hipLaunchKernelGGL(kern, grid, dim3(256), LDS_BYTES, st, p);
     return check_launch("peneo_attn_fwd(pipe)");
   };

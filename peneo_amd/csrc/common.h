@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <cstdlib>
 
 #include "../../include/peneo_hip.h"
 
@@ -29,6 +30,22 @@ int order_dependent(const char* entry_point);
     const int od_rc_ = ::peneo::order_dependent(entry_point);     \
     if (od_rc_ != PENEO_OK) return od_rc_;                        \
   } while (0)
+
+// A kernel may use more dynamic LDS than the default only once that is set for it.  raise_dynamic_lds sets it, on every call
+// (allow_dynamic_lds in gemm_common.h is the once-per-device form), and returns PENEO_OK or, with the one spelling of the error
+// (dynamic_lds_error), PENEO_ERR_LAUNCH.
+inline int dynamic_lds_error(const char* entry_point, size_t bytes) {
+  set_error("%s: cannot raise dynamic LDS to %zu bytes", entry_point, bytes);
+  return PENEO_ERR_LAUNCH;
+}
+template <typename KernelT>
+inline int raise_dynamic_lds(KernelT kernel, size_t bytes, const char* entry_point) {
+  const void* fn = reinterpret_cast<const void*>(kernel);
+  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess) return PENEO_OK;
+  return dynamic_lds_error(entry_point, bytes);
+}
+// an on / off switch of the environment: on unless the variable is set to 0 (a caller keeps the answer in a function-local static)
+inline bool env_switch_on(const char* name) { const char* e = getenv(name); return !e || atoi(e) != 0; }
 
 #define PENEO_REQUIRE(cond, ...)                \
   do {                                          \
@@ -98,7 +115,8 @@ template <> __device__ __forceinline__ uint4 pack16<bf16_t>(const float* in) {
 // v_exp_f32 / v_rcp_f32 (1 ulp) instead of the IEEE-division / denormal-safe library forms: an fp32 divide is
 // ~10 VALU instructions, and SiLU runs on every one of the nh*D hidden units of every token pair.
 __device__ __forceinline__ float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
-__device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }
+constexpr float kLog2e = 1.4426950408889634f;
+__device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp2f(x * kLog2e); }
 __device__ __forceinline__ float sigmoid_f(float x) { return fast_rcp(1.0f + fast_exp(-x)); }
 __device__ __forceinline__ float silu_f(float x) { return x * sigmoid_f(x); }
 __device__ __forceinline__ float silu_grad_f(float x) {

@@ -392,11 +392,8 @@ extern "C" int peneo_embed_text_bwd(int dtype, const void* d_out, int64_t rpb, i
     dim3 bgrid((unsigned)((rows + EBX_TOK - 1) / EBX_TOK));
 #define PENEO_EBX_LAUNCH(T_)                                                                                                      \
   {                                                                                                                               \
-    if (box_lds > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(embed_box_bwd_kernel<T_>),                       \
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)box_lds) != hipSuccess) {     \
-      set_error("peneo_embed_text_bwd: cannot raise dynamic LDS to %zu bytes", box_lds);                                          \
+    if (box_lds > 48 * 1024 && raise_dynamic_lds(embed_box_bwd_kernel<T_>, box_lds, "peneo_embed_text_bwd") != PENEO_OK)          \
       return PENEO_ERR_LAUNCH;                                                                                                    \
-    }                                                                                                                             \
     hipLaunchKernelGGL(embed_box_bwd_kernel<T_>, bgrid, dim3(256), box_lds, (hipStream_t)stream, (const T_*)d_out, rpb, bstride,  \
                        bbox, *g, coord_size, shape_size, max_2d, rows, H, clip_hw);                                               \
   }

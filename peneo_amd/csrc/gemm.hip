@@ -214,7 +214,7 @@ __device__ __forceinline__ void tile_epilogue(const GemmParams& p, f32x16_t (&ac
         w2p[j] = f2{w2c[2][2 * j], w2c[2][2 * j + 1]}; b1p[j] = f2{b1v[2 * j], b1v[2 * j + 1]};
         s0p[j] = f2{0.f, 0.f}; s1p[j] = s0p[j]; s2p[j] = s0p[j]; sbp[j] = s0p[j];
       }
-      const f2 one2 = f2{1.f, 1.f}, nl2e = f2{-1.4426950408889634f, -1.4426950408889634f};
+      const f2 one2 = f2{1.f, 1.f}, nl2e = f2{-kLog2e, -kLog2e};
 #pragma unroll 2
       for (int i = 0; i < GB / 16; ++i) {
         const int r = rl + 16 * i;
@@ -449,8 +449,6 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmParams p) {
 // the k tail reads a zero line.
 // ================================================================================================
 __device__ __attribute__((aligned(16))) uint32_t g_zero_line[4] = {0u, 0u, 0u, 0u};
-
-typedef short s16x4_t __attribute__((ext_vector_type(4)));
 
 struct DmaSrc { const char* p[4]; };
 
@@ -860,8 +858,7 @@ static int launch_gemm(const GemmParams& p, bool ak, bool bk, dim3 grid, hipStre
   size_t shmem = 4 * TILE_BYTES + (p.dz_on ? 2 * GB * 4 * sizeof(float) : 0);
   if (p.dz_on) {
     if (!(ak && bk)) { set_error("peneo_gemm: pair_dz needs k-major A and B"); return PENEO_ERR_INVALID; }
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_kernel<T, true, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)shmem) != hipSuccess) { set_error("peneo_gemm: cannot raise dynamic LDS"); return PENEO_ERR_LAUNCH; }
+    if (raise_dynamic_lds(gemm_kernel<T, true, true, true>, shmem, "peneo_gemm") != PENEO_OK) return PENEO_ERR_LAUNCH;
     hipLaunchKernelGGL((gemm_kernel<T, true, true, true>), grid, dim3(256), shmem, st, p);
     return check_launch("peneo_gemm");
   }
@@ -876,8 +873,7 @@ static int launch_gemm_dma_pipe(const GemmParams& p, bool ak, bool bk, dim3 grid
   size_t shmem = 4 * TILE_BYTES + (p.dz_on ? 2 * GB * 4 * sizeof(float) : 0);
   if (p.dz_on) {
     if (!(ak && bk)) { set_error("peneo_gemm: pair_dz needs k-major A and B"); return PENEO_ERR_INVALID; }
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_dma_pipe_kernel<true, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)shmem) != hipSuccess) { set_error("peneo_gemm: cannot raise dynamic LDS"); return PENEO_ERR_LAUNCH; }
+    if (raise_dynamic_lds(gemm_dma_pipe_kernel<true, true, false, true>, shmem, "peneo_gemm") != PENEO_OK) return PENEO_ERR_LAUNCH;
     hipLaunchKernelGGL((gemm_dma_pipe_kernel<true, true, false, true>), grid, dim3(256), shmem, st, p);
     return check_launch("peneo_gemm");
   }
@@ -948,10 +944,8 @@ extern "C" int peneo_gemm_group(int dtype, int a_kmajor, int b_kmajor, int c_dty
 #define PENEO_GROUP_LAUNCH(AK_, BK_)                                                                                         \
   {                                                                                                                          \
     static std::atomic<uint64_t> lds_devices{0};                                                                             \
-    if (!allow_dynamic_lds(reinterpret_cast<const void*>(gemm_dma_pipe_group_kernel<AK_, BK_>), shmem, lds_devices)) {       \
-      set_error("peneo_gemm_group: cannot raise dynamic LDS to %d bytes", shmem);                                            \
-      return PENEO_ERR_LAUNCH;                                                                                               \
-    }                                                                                                                        \
+    if (!allow_dynamic_lds(reinterpret_cast<const void*>(gemm_dma_pipe_group_kernel<AK_, BK_>), shmem, lds_devices))         \
+      return dynamic_lds_error("peneo_gemm_group", shmem);                                                                   \
     hipLaunchKernelGGL((gemm_dma_pipe_group_kernel<AK_, BK_>), dim3((unsigned)tiles), dim3(256), shmem, st, g);              \
   }
   if (ak && bk) PENEO_GROUP_LAUNCH(true, true)

@@ -282,10 +282,8 @@ template <typename C, bool PART = false>
 static int launch_big(const GemmParams& p, hipStream_t st) {
   const int tm = (p.M + C::BM - 1) / C::BM, tn = (p.N + C::BN - 1) / C::BN;
   static std::atomic<uint64_t> lds_devices{0};
-  if (!allow_dynamic_lds(reinterpret_cast<const void*>(gemm_big_kernel<C, PART>), C::LDS_BYTES, lds_devices)) {
-    set_error("peneo_gemm: cannot raise dynamic LDS to %d bytes", C::LDS_BYTES);
-    return PENEO_ERR_LAUNCH;
-  }
+  if (!allow_dynamic_lds(reinterpret_cast<const void*>(gemm_big_kernel<C, PART>), C::LDS_BYTES, lds_devices))
+    return dynamic_lds_error("peneo_gemm", C::LDS_BYTES);
   const int wgs = tm * tn * (PART ? p.split_k : 1);
   hipLaunchKernelGGL((gemm_big_kernel<C, PART>), dim3((unsigned)wgs), dim3(512), C::LDS_BYTES, st, p, tn);
   const int rc = check_launch("peneo_gemm (big tiles)");
@@ -316,16 +314,20 @@ static double small_cost(int M, int N) {
 }
 
 static int g_big_mode = -1;   // PENEO_GEMM_BIG: 0 = off, 1 = auto (default), 256 / 384 / 128 = force that tile where it applies
+static int big_mode() {       // (read on first use, unless peneo_gemm_set_big_mode came first)
+  if (g_big_mode < 0) { const char* e = getenv("PENEO_GEMM_BIG"); g_big_mode = e ? atoi(e) : 1; }
+  return g_big_mode;
+}
 
 int launch_gemm_big(const GemmParams& p, bool b_kmajor, hipStream_t st) {
-  if (g_big_mode < 0) { const char* e = getenv("PENEO_GEMM_BIG"); g_big_mode = e ? atoi(e) : 1; }
-  if (g_big_mode == 0) return 0;
+  const int mode = big_mode();
+  if (mode == 0) return 0;
   // mn-major B = the dgrad GEMMs of the backward: in the step they run beside the weight-gradient stream, and a workgroup that
   // needs a CU's whole LDS cannot share it (measured: d_zi on 384 x 192 tiles 50 us alone, 166 us in the step; the step is
   // 0.2 ms FASTER with the 128 x 128 kernel there).  A forced tile (tools) still runs them.
   // (Those are SHORT launches that wait for empty CUs each time.  The one LONG launch of the step, the pair heads' dW1 on the side
   // stream, does run on whole-LDS workgroups: launch_gemm_big_nn.)
-  if (!b_kmajor && g_big_mode == 1) return 0;
+  if (!b_kmajor && mode == 1) return 0;
   if (p.split_k > 1 || p.dz_on || p.K % 64 != 0 || p.K < 128 || p.N % 8 != 0) return 0;
   if ((reinterpret_cast<uintptr_t>(p.A) | reinterpret_cast<uintptr_t>(p.B)) & 15) return 0;
   if ((p.lda * 2) % 16 != 0 || (p.ldb * 2) % 16 != 0) return 0;
@@ -340,7 +342,7 @@ int launch_gemm_big(const GemmParams& p, bool b_kmajor, hipStream_t st) {
       return 0;
   }
   if ((int64_t)p.M * p.N < (int64_t)1 << 21 || p.M < 256 || p.N < 128) return 0;   // small problems: the 128 x 128 kernel fills the chip better
-  int pick = g_big_mode;
+  int pick = mode;
   if (pick == 1) {
     const double c256 = big_cost(p.M, p.N, 256, 256, 5080.0), c384 = big_cost(p.M, p.N, 384, 192, 5550.0);
     const double c128 = b_kmajor ? big_cost(p.M, p.N, 256, 128, 2760.0) : 1e30;   // mn-major B: measured behind the 128 x 128 kernel
@@ -381,8 +383,7 @@ static std::atomic<uint64_t> g_nn_launches{0};   // calls that took the path (th
 
 static int nn_mode() {
   if (g_nn_mode < 0) { const char* e = getenv("PENEO_GEMM_NN384"); g_nn_mode = e ? atoi(e) : 1; }
-  if (g_big_mode < 0) { const char* e = getenv("PENEO_GEMM_BIG"); g_big_mode = e ? atoi(e) : 1; }
-  return g_big_mode == 0 ? 0 : g_nn_mode;      // PENEO_GEMM_BIG=0 switches every big-tile path off
+  return big_mode() == 0 ? 0 : g_nn_mode;      // PENEO_GEMM_BIG=0 switches every big-tile path off
 }
 
 // the shape part of the rule under the mode in force: the one copy, also what a caller sizes its split-k by (peneo_gemm_nn384_shape_ok)
@@ -412,10 +413,7 @@ int launch_gemm_big_nn(const GemmParams& p, hipStream_t st) {
 
 /* tools/ only (not in the header): 0 = off, 1 = choose by the cost model, 256 / 384 / 128 = force that tile shape */
 extern "C" void peneo_gemm_set_big_mode(int mode) { peneo::g_big_mode = mode; }
-extern "C" int peneo_gemm_big_mode(void) {
-  if (peneo::g_big_mode < 0) { const char* e = getenv("PENEO_GEMM_BIG"); peneo::g_big_mode = e ? atoi(e) : 1; }
-  return peneo::g_big_mode;
-}
+extern "C" int peneo_gemm_big_mode(void) { return peneo::big_mode(); }
 /* 0 = off, 1 = the rule of launch_gemm_big_nn, 2 = that rule without its bound on K */
 extern "C" void peneo_gemm_set_nn384_mode(int mode) { peneo::g_nn_mode = mode; }
 extern "C" int peneo_gemm_nn384_mode(void) { return peneo::nn_mode(); }

@@ -251,10 +251,8 @@ extern "C" int peneo_gemm_mxfp8(int M, int N, int K, const void* A_q, const void
   }
   p.Cq = static_cast<uint8_t*>(C_q); p.Cs = static_cast<uint8_t*>(C_s);
   static std::atomic<uint64_t> devices{0};
-  if (!allow_dynamic_lds(reinterpret_cast<const void*>(gemm_mx_kernel), MXG_LDS, devices)) {
-    set_error("peneo_gemm_mxfp8: cannot raise dynamic LDS to %d bytes", MXG_LDS);
-    return PENEO_ERR_LAUNCH;
-  }
+  if (!allow_dynamic_lds(reinterpret_cast<const void*>(gemm_mx_kernel), MXG_LDS, devices))
+    return dynamic_lds_error("peneo_gemm_mxfp8", MXG_LDS);
   const dim3 grid((unsigned)(((N + MXG_TILE - 1) / MXG_TILE) * ((M + MXG_TILE - 1) / MXG_TILE)));
   hipLaunchKernelGGL(gemm_mx_kernel, grid, dim3(256), MXG_LDS, (hipStream_t)stream, p);
   return check_launch("peneo_gemm_mxfp8");

@@ -467,10 +467,8 @@ static int launch_sk_ep(const GemmParams& p, void* ws, hipStream_t st) {
   pl.G = G;
   pl.prof = g_sk_prof;
   static std::atomic<uint64_t> lds_devices{0};
-  if (!allow_dynamic_lds(reinterpret_cast<const void*>(gemm_sk_kernel<C, EP>), C::LDS_BYTES, lds_devices)) {
-    set_error("peneo_gemm: cannot raise dynamic LDS to %d bytes", C::LDS_BYTES);
-    return PENEO_ERR_LAUNCH;
-  }
+  if (!allow_dynamic_lds(reinterpret_cast<const void*>(gemm_sk_kernel<C, EP>), C::LDS_BYTES, lds_devices))
+    return dynamic_lds_error("peneo_gemm", C::LDS_BYTES);
   // every flag the launch polls starts at 0.  A kernel, not hipMemsetAsync: as a memset node of a captured graph it was replayed
   // out of order with the stream's other work when another queue was busy (the replay's result stale or half written: DESIGN 16)
   if (pl.flags) {

@@ -372,7 +372,7 @@ __global__ __launch_bounds__(PW_WAVES * 64, 2) void pair_bwd_ws_kernel(PairBwdPa
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_wave_barrier();
     };
-    const f2 nl2e = f2{-1.4426950408889634f, -1.4426950408889634f};
+    const f2 nl2e = f2{-kLog2e, -kLog2e};
 
     // one producer iteration: Z(s+1) accumulates into zw (fragments hand-issued one chunk ahead, two register sets, each
     // re-loaded only BEHIND the following chunk's MFMAs); E(s) reads zr (written during the previous iteration)
@@ -863,7 +863,7 @@ __global__ __launch_bounds__(PW_WAVES * 64, 2) void pair_bwd_sv_kernel(PairBwdPa
                                : (uint32_t)(((lane >> 4) & 1) * 1024 + ((4 * (half ^ ((lane >> 4) & 1)) + ((lane & 15) >> 2)) * 32) + (lane & 3) * 8);
     const uint32_t tbase = lds_addr(sT) + grp * 2048 + half * 256 + ((2 * r32) & 15);
     const uint32_t tA0 = tbase + ((((r32 >> 3) ^ half)) << 4), tB0 = tbase + ((((r32 >> 3) ^ half ^ 2)) << 4);
-    const float nl2e = -1.4426950408889634f;
+    const float nl2e = -kLog2e;
     __syncthreads();                                          // sW2p visible (matches the consumers' barrier)
     int rslot = 0;                                            // s % PSV_NR
     for (int s = 0; s < nslab; ++s) {
@@ -1236,7 +1236,7 @@ __global__ __launch_bounds__(PB_WAVES * 64, 1) void pair_bwd_one_kernel(PairBwdP
     gT0 = pb_u32x4{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7])};
     gT1 = pb_u32x4{pack_bf16x2(v[8], v[9]), pack_bf16x2(v[10], v[11]), pack_bf16x2(v[12], v[13]), pack_bf16x2(v[14], v[15])};
   };
-  const f2 nl2e = f2{-1.4426950408889634f, -1.4426950408889634f};
+  const f2 nl2e = f2{-kLog2e, -kLog2e};
   // 16-bit selectors of the dz tile's dword: even lanes (own.lo, partner.lo), odd lanes (partner.hi, own.hi)
   const uint32_t psel = (lane & 1) ? 0x03020706u : 0x05040100u;
   const int t_swz = (r32 >> 2) & 3;
@@ -1567,10 +1567,7 @@ static int launch_pair_bwd_one(const PairBwdParams& p, hipStream_t st) {
   const size_t red = (size_t)4 * (KS / 2) * 16 * 32 * sizeof(float);
   if (sh < red) sh = red;
   if (sh > 160 * 1024) { set_error("peneo_pair_bwd_fused: D=%d needs %zu bytes of LDS", p.D, sh); return PENEO_ERR_INVALID; }
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(pair_bwd_one_kernel<KS, DROP, OWN>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh) != hipSuccess) {
-    set_error("peneo_pair_bwd_fused: cannot raise dynamic LDS to %zu bytes", sh);
-    return PENEO_ERR_LAUNCH;
-  }
+  if (raise_dynamic_lds(pair_bwd_one_kernel<KS, DROP, OWN>, sh, "peneo_pair_bwd_fused") != PENEO_OK) return PENEO_ERR_LAUNCH;
   hipLaunchKernelGGL((pair_bwd_one_kernel<KS, DROP, OWN>), dim3((unsigned)p.ntiles, (unsigned)p.B), dim3(PB_WAVES * 64), sh, st, p);
   return check_launch("peneo_pair_bwd_fused");
 }
@@ -1580,11 +1577,7 @@ static int launch_pair_bwd_ws(const PairBwdParams& p, hipStream_t st) {
   const int ncol = p.a.num_heads * p.D;
   const size_t sh = (size_t)4 * KS * 1024 + (size_t)ncol * 12 + (size_t)4 * 32 * 16 * 3 + (size_t)2 * 4 * 2048 + (size_t)2 * 4 * 32 * 32 * 2;
   if (sh > 160 * 1024) { set_error("peneo_pair_bwd_fused: D=%d needs %zu bytes of LDS", p.D, sh); return PENEO_ERR_INVALID; }
-  if (sh > 64 * 1024 &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(pair_bwd_ws_kernel<KS, DROP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh) != hipSuccess) {
-    set_error("peneo_pair_bwd_fused: cannot raise dynamic LDS to %zu bytes", sh);
-    return PENEO_ERR_LAUNCH;
-  }
+  if (sh > 64 * 1024 && raise_dynamic_lds(pair_bwd_ws_kernel<KS, DROP>, sh, "peneo_pair_bwd_fused") != PENEO_OK) return PENEO_ERR_LAUNCH;
   hipLaunchKernelGGL((pair_bwd_ws_kernel<KS, DROP>), dim3((unsigned)p.ntiles, (unsigned)p.B), dim3(PW_WAVES * 64), sh, st, p);
   return check_launch("peneo_pair_bwd_fused");
 }
@@ -1595,10 +1588,7 @@ static int launch_pair_bwd_sv(const PairBwdParams& p, hipStream_t st) {
   constexpr const char* who = E4M3 ? "peneo_pair_bwd_saved_e4m3" : "peneo_pair_bwd_saved";
   const size_t sh = (size_t)3 * KS * 1024 + (size_t)PSV_NR * 4 * (E4M3 ? PB_REC8_BYTES : PB_REC_BYTES) + (size_t)ncol * 8 + (size_t)4 * 32 * 16 * 3 + (size_t)2 * 4 * 2048;
   if (sh > 160 * 1024) { set_error("%s: D=%d with %d heads needs %zu bytes of LDS", who, p.D, p.a.num_heads, sh); return PENEO_ERR_INVALID; }
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(pair_bwd_sv_kernel<KS, DROP, E4M3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh) != hipSuccess) {
-    set_error("%s: cannot raise dynamic LDS to %zu bytes", who, sh);
-    return PENEO_ERR_LAUNCH;
-  }
+  if (raise_dynamic_lds(pair_bwd_sv_kernel<KS, DROP, E4M3>, sh, who) != PENEO_OK) return PENEO_ERR_LAUNCH;
   hipLaunchKernelGGL((pair_bwd_sv_kernel<KS, DROP, E4M3>), dim3((unsigned)p.ntiles, (unsigned)p.B), dim3(PW_WAVES * 64), sh, st, p);
   return check_launch(who);
 }

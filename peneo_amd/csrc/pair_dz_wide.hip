@@ -71,7 +71,7 @@ __global__ __launch_bounds__(DW_WAVES * 64, 1) void pair_dz_wide_kernel(DzFusedP
     }
   };
   typedef float f2 __attribute__((ext_vector_type(2)));
-  const f2 one2 = f2{1.f, 1.f}, nl2e = f2{-1.4426950408889634f, -1.4426950408889634f};
+  const f2 one2 = f2{1.f, 1.f}, nl2e = f2{-kLog2e, -kLog2e};
   const float4* myG = sG + wave * 32;
   const bool odd = (lane & 1) != 0;
 
@@ -244,10 +244,7 @@ bool pair_dz_wide_supported(int dtype, int D, int num_heads) {
 template <int KS>
 static int launch_pair_dz_wide(const DzFusedParams& p, hipStream_t st) {
   const size_t sh = pair_dz_wide_lds_bytes(p.D);
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(pair_dz_wide_kernel<KS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh) != hipSuccess) {
-    set_error("peneo_pair_dz_fused: cannot raise dynamic LDS to %zu bytes", sh);
-    return PENEO_ERR_LAUNCH;
-  }
+  if (raise_dynamic_lds(pair_dz_wide_kernel<KS>, sh, "peneo_pair_dz_fused") != PENEO_OK) return PENEO_ERR_LAUNCH;
   const int64_t blocks = (p.npairs + DW_PAIRS - 1) / DW_PAIRS;
   hipLaunchKernelGGL((pair_dz_wide_kernel<KS>), dim3((unsigned)blocks), dim3(DW_WAVES * 64), sh, st, p);
   return check_launch("peneo_pair_dz_fused");

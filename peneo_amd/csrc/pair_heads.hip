@@ -999,7 +999,7 @@ __global__ __launch_bounds__(PH_WAVES * 64, 2) void pair_heads_fwd_hand_kernel(P
       constexpr int Q = decltype(qc)::value, G = Q / 6, S = Q % 6;
       if constexpr (S == 0) {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) { t[e] = zr[4 * G + e]; u[e] = t[e] * -1.4426950408889634f; }
+        for (int e = 0; e < 4; ++e) { t[e] = zr[4 * G + e]; u[e] = t[e] * -kLog2e; }
         if constexpr (SAVE) { zp[2 * G] = pack_f16x2(t[0], t[1]); zp[2 * G + 1] = pack_f16x2(t[2], t[3]); }
       } else if constexpr (S == 1) {
 #pragma unroll
@@ -1137,10 +1137,7 @@ static int launch_pair_fwd_hand(const PairFwdParams& p, hipStream_t st) {
   const size_t nstage = 4 * slab + 5 * 512 * 4 <= 160 * 1024 ? 4 : 3;      // as in the kernel
   size_t sh = nstage * slab + (size_t)p.num_heads * p.D * sizeof(float);
   if (sh > 160 * 1024) { set_error("%s: D=%d needs %zu bytes of LDS", who, p.D, sh); return PENEO_ERR_INVALID; }
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(pair_heads_fwd_hand_kernel<KS, DROP, SAVE, E4M3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh) != hipSuccess) {
-    set_error("%s: cannot raise dynamic LDS to %zu bytes", who, sh);
-    return PENEO_ERR_LAUNCH;
-  }
+  if (raise_dynamic_lds(pair_heads_fwd_hand_kernel<KS, DROP, SAVE, E4M3>, sh, who) != PENEO_OK) return PENEO_ERR_LAUNCH;
   dim3 grid(SAVE ? (unsigned)((p.ntiles + 1) / 2) : (unsigned)((p.P + PH_PAIRS - 1) / PH_PAIRS), p.B);
   hipLaunchKernelGGL((pair_heads_fwd_hand_kernel<KS, DROP, SAVE, E4M3>), grid, dim3(PH_WAVES * 64), sh, st, p);
   return check_launch(who);
@@ -1153,12 +1150,7 @@ static int launch_pair_fwd_v(const PairFwdParams& p, hipStream_t st) {
   size_t sh = NSTAGE * slab + (size_t)p.num_heads * p.D * sizeof(float);
   if (sh < (size_t)PH_WAVES * 32 * sizeof(float)) sh = (size_t)PH_WAVES * 32 * sizeof(float);
   if (sh > 160 * 1024) { set_error("peneo_pair_heads_fwd: D=%d needs %zu bytes of LDS", p.D, sh); return PENEO_ERR_INVALID; }
-  if (sh > 64 * 1024) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(pair_heads_fwd_kernel<T, KS, NSTAGE, VARIANT, DROP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh) != hipSuccess) {
-      set_error("peneo_pair_heads_fwd: cannot raise dynamic LDS to %zu bytes", sh);
-      return PENEO_ERR_LAUNCH;
-    }
-  }
+  if (sh > 64 * 1024 && raise_dynamic_lds(pair_heads_fwd_kernel<T, KS, NSTAGE, VARIANT, DROP>, sh, "peneo_pair_heads_fwd") != PENEO_OK) return PENEO_ERR_LAUNCH;
   dim3 grid((unsigned)((p.P + PH_PAIRS - 1) / PH_PAIRS), p.B);
   hipLaunchKernelGGL((pair_heads_fwd_kernel<T, KS, NSTAGE, VARIANT, DROP>), grid, dim3(PH_WAVES * 64), sh, st, p);
   return check_launch("peneo_pair_heads_fwd");
@@ -1168,7 +1160,7 @@ static int launch_pair_fwd_v(const PairFwdParams& p, hipStream_t st) {
 // (the compiler drains the whole vm counter in front of every ds_read while a DMA it knows about is in flight)
 constexpr int PH_DEFAULT_VARIANT = 1;
 // tools/: PENEO_PAIR_FWD_HAND=0 selects the generic kernel at D = 384 / 512 too
-static bool pair_fwd_hand() { static const bool v = [] { const char* e = getenv("PENEO_PAIR_FWD_HAND"); return !e || atoi(e) != 0; }(); return v; }
+static bool pair_fwd_hand() { static const bool v = env_switch_on("PENEO_PAIR_FWD_HAND"); return v; }
 template <typename T, int KS>
 static int launch_pair_fwd(const PairFwdParams& p, hipStream_t st) {
   constexpr int V = sizeof(T) == 2 ? PH_DEFAULT_VARIANT : 0;
@@ -1334,7 +1326,7 @@ __global__ __launch_bounds__(PH_WAVES * 64, 2) void pair_dz_fused_kernel(DzFused
     }
   };
   typedef float f2 __attribute__((ext_vector_type(2)));
-  const f2 one2 = f2{1.f, 1.f}, nl2e = f2{-1.4426950408889634f, -1.4426950408889634f};
+  const f2 one2 = f2{1.f, 1.f}, nl2e = f2{-kLog2e, -kLog2e};
   const float4* myG = sG + wave * 32;
   const int nrows = (int)min((int64_t)32, p.npairs - lp0);   // valid pairs of this wave's tile (may be <= 0)
 
@@ -1481,11 +1473,7 @@ static int launch_pair_dz_fused_v(const DzFusedParams& p, hipStream_t st) {
   const int ncol = p.a.num_heads * p.D;
   const size_t sh = (KS > 24 ? 2 : 3) * (size_t)slab_stride_bytes(KS * 16, 2) + (size_t)ncol * 16 + (size_t)PH_WAVES * 32 * 16 * 3;
   if (sh > 160 * 1024) { set_error("peneo_pair_dz_fused: D=%d needs %zu bytes of LDS", p.D, sh); return PENEO_ERR_INVALID; }
-  if (sh > 64 * 1024 &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(pair_dz_fused_kernel<KS, PIPE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh) != hipSuccess) {
-    set_error("peneo_pair_dz_fused: cannot raise dynamic LDS to %zu bytes", sh);
-    return PENEO_ERR_LAUNCH;
-  }
+  if (sh > 64 * 1024 && raise_dynamic_lds(pair_dz_fused_kernel<KS, PIPE>, sh, "peneo_pair_dz_fused") != PENEO_OK) return PENEO_ERR_LAUNCH;
   const int64_t blocks = (p.npairs + PH_PAIRS - 1) / PH_PAIRS;
   hipLaunchKernelGGL((pair_dz_fused_kernel<KS, PIPE>), dim3((unsigned)blocks), dim3(PH_WAVES * 64), sh, st, p);
   return check_launch("peneo_pair_dz_fused");

@@ -336,11 +336,7 @@ int launch_mx_fwd(const MxFwdParams& p, hipStream_t st) {
   size_t sh = (size_t)NSTAGE * mx_slab_bytes(KS8) + (size_t)p.num_heads * p.D * sizeof(float);
   if (sh < (size_t)MX_WAVES * 32 * sizeof(float)) sh = (size_t)MX_WAVES * 32 * sizeof(float);
   if (sh > 160 * 1024) { set_error("peneo_pair_heads_fwd_mxfp8: D=%d, %d heads need %zu bytes of LDS", p.D, p.num_heads, sh); return PENEO_ERR_INVALID; }
-  if (sh > 64 * 1024 &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(pair_heads_mx_fwd_kernel<KS8, NSTAGE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh) != hipSuccess) {
-    set_error("peneo_pair_heads_fwd_mxfp8: cannot raise dynamic LDS to %zu bytes", sh);
-    return PENEO_ERR_LAUNCH;
-  }
+  if (sh > 64 * 1024 && raise_dynamic_lds(pair_heads_mx_fwd_kernel<KS8, NSTAGE>, sh, "peneo_pair_heads_fwd_mxfp8") != PENEO_OK) return PENEO_ERR_LAUNCH;
   dim3 grid((unsigned)((p.P + MX_PAIRS - 1) / MX_PAIRS), p.B);
   hipLaunchKernelGGL((pair_heads_mx_fwd_kernel<KS8, NSTAGE>), grid, dim3(MX_WAVES * 64), sh, st, p);
   return check_launch("peneo_pair_heads_fwd_mxfp8");
@@ -631,10 +627,7 @@ int launch_mx_save(const MxSaveParams& q, hipStream_t st) {
   if (sh > 160 * 1024) { set_error("peneo_pair_heads_fwd_mxfp8_save: D=%d, %d heads need %zu bytes of LDS", q.f.D, q.f.num_heads, sh); return PENEO_ERR_INVALID; }
   const void* fn = q.drop_thr16 ? reinterpret_cast<const void*>(pair_heads_mx_save_kernel<KS8, NSTAGE, true>)
                                 : reinterpret_cast<const void*>(pair_heads_mx_save_kernel<KS8, NSTAGE, false>);
-  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh) != hipSuccess) {
-    set_error("peneo_pair_heads_fwd_mxfp8_save: cannot raise dynamic LDS to %zu bytes", sh);
-    return PENEO_ERR_LAUNCH;
-  }
+  if (raise_dynamic_lds(fn, sh, "peneo_pair_heads_fwd_mxfp8_save") != PENEO_OK) return PENEO_ERR_LAUNCH;
   dim3 grid((unsigned)((q.ntiles + 1) / 2), q.f.B);
   if (q.drop_thr16) hipLaunchKernelGGL((pair_heads_mx_save_kernel<KS8, NSTAGE, true>), grid, dim3(MX_WAVES * 64), sh, st, q);
   else hipLaunchKernelGGL((pair_heads_mx_save_kernel<KS8, NSTAGE, false>), grid, dim3(MX_WAVES * 64), sh, st, q);

@@ -154,10 +154,7 @@ bool pair_wide_supported(int dtype, int D, int num_heads) {
 template <int KS, bool DROP>
 static int launch_pair_wide(const PairFwdParams& p, hipStream_t st) {
   const size_t sh = pair_wide_lds_bytes(p.D, p.num_heads);
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(pair_heads_wide_kernel<KS, DROP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh) != hipSuccess) {
-    set_error("peneo_pair_heads_fwd: cannot raise dynamic LDS to %zu bytes", sh);
-    return PENEO_ERR_LAUNCH;
-  }
+  if (raise_dynamic_lds(pair_heads_wide_kernel<KS, DROP>, sh, "peneo_pair_heads_fwd") != PENEO_OK) return PENEO_ERR_LAUNCH;
   dim3 grid((unsigned)((p.P + PW_PAIRS - 1) / PW_PAIRS), p.B);
   hipLaunchKernelGGL((pair_heads_wide_kernel<KS, DROP>), grid, dim3(PW_WAVES * 64), sh, st, p);
   return check_launch("peneo_pair_heads_fwd");

@@ -221,7 +221,7 @@ extern "C" int peneo_encoder_layer_bwd(const peneo_encoder_layer* L, const peneo
   // them beside the attention backward (3 of 3 interleaved pairs, profiles/r05_ab_runs.txt; round 2 had measured the grouped
   // launch 0.3 ms BEHIND: the attention kernels it ran beside were latency-bound then and are bound by memory and issue now).
   // Serial mode (no side stream: profiling) and PENEO_WGRAD_GROUP=0 keep the per-GEMM launches.
-  static const bool group_on = [] { const char* e = getenv("PENEO_WGRAD_GROUP"); return !e || atoi(e) != 0; }();
+  static const bool group_on = env_switch_on("PENEO_WGRAD_GROUP");
   const bool grouped = group_on && side != main;
   STAGE_TRY(peneo_colsum(PENEO_BF16, d_dense2, H, R, H, G->dbo2, 1, side));
   if (!grouped) STAGE_TRY(gemm(0, 0, H, I, R, d_dense2, H, L->inter, I, G->dwo2, I, PENEO_F32, ep, wsd, side));
