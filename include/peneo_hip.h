@@ -423,6 +423,34 @@ int peneo_pair_heads_fwd(int dtype, const void* ab, int B, int N, const peneo_pa
                          float* const* logits /* host array of num_heads device pointers, or NULL */,
                          const peneo_pair_loss* loss, peneo_stream_t stream);
 
+/* Length-aware inference form (version 111, opt-in): peneo_pair_heads_fwd that skips the pairs touching a document's padding.
+ * lens [B] int32 on the device, clamped to [0, N] by the kernels; n_b = the clamped length of document b, P_b = n_b (n_b + 1) / 2.
+ * WALK: document b is walked as the n_b-token document it is - workgroup x owns its local pairs q in [256 x, 256 x + 256), (i, j) is
+ *   pair q of an n_b-token triangle, live while q < P_b - and everything indexed by the pair (logits, tags) keeps the N-packed index
+ *   p(i, j) above; ab keeps its [B, N, 2D] strides.  The grid stays (ceil(P / 256), B): the lengths are never read by the host.  A
+ *   workgroup without a live pair leaves at once, storing a zero row of loss partials.  With n_b = N the walk is peneo_pair_heads_fwd's.
+ * LIVE PAIRS (j < n_b): everything of peneo_pair_heads_fwd holds - the packed weights of peneo_pair_heads_pack, the widths and dtypes
+ *   of peneo_pair_heads_supported, and the logits bit for bit (the arithmetic of a pair does not depend on where it is walked).
+ * PADDED PAIRS (j >= n_b) hold the background row in every requested map: class 0 = 0.0f, every other class = PENEO_PAIR_PAD_LOGIT.
+ *   Their argmax is tag 0 with score 1, so peneo_spots_compact* and every other consumer of the [B, P, C] maps work unchanged.  (A fill
+ *   launch of the same call, ahead of the main kernel on the stream: every element of every requested map is defined after the call.)
+ * LOSS (`loss` may be NULL; loss->dlogits[h] must be NULL): the peneo_pair_loss_partials(B, N) partial rows sum w nll, w and the class
+ *   sums over the LIVE PAIRS ONLY; rows of workgroups without a live pair are zero.  The rows of document b are, row by row, the
+ *   bits peneo_pair_heads_fwd writes for that document cropped to n_b tokens.  peneo_loss_finish over them is therefore A DIFFERENT
+ *   NUMBER from the reference's loss and from peneo_pair_heads_fwd's, which average over the padded pairs (label 0) as well: it is the
+ *   class-weighted mean over the pairs of real tokens.  (With no live pair in the whole batch the mean is 0 / 0.)
+ * Returns PENEO_ERR_INVALID with a peneo_last_error() text, nothing launched, for desc->drop_p != 0, a NULL lens, a non-NULL dlogits
+ * and an unsupported (dtype, D, heads).  No workspace, no allocation, no host synchronisation; safe under graph capture; nothing
+ * order-dependent is launched.
+ * peneo_pair_lens_from_mask: lens[b] = 1 + the last index j < N with mask[b * ld + j] != 0, 0 if there is none, N for a NULL mask (one
+ * launch; mask int64 on the device, row stride ld >= N).  A mask that is not a prefix yields a superset of its tokens, never a subset. */
+#define PENEO_PAIR_PAD_LOGIT (-1e30f)
+int peneo_pair_lens_from_mask(const int64_t* mask /* [B, ld] or NULL */, int64_t ld, int B, int N,
+                              int32_t* lens, peneo_stream_t stream);
+int peneo_pair_heads_fwd_lens(int dtype, const void* ab, int B, int N, const int32_t* lens,
+                              const peneo_pair_heads_desc* desc, float* const* logits,
+                              const peneo_pair_loss* loss, peneo_stream_t stream);
+
 /* The same launch for a train step whose backward is peneo_pair_bwd_saved (bf16, D = 384: peneo_pair_save_supported).  It walks the
  * pairs in the backward's blocks of 8 rows i x 16 columns j and leaves what the backward would otherwise rebuild:
  *   act    [peneo_pair_save_bytes(B, N, num_heads, D)]: per document, block, 32-unit slab of the num_heads * D hidden units and

@@ -20,9 +20,20 @@ struct PairFwdParams {
   uint32_t drop_thr16, drop_seed; float drop_scale;   // K12 dropout (common.h: pair_drop_*): threshold 0 = off, scale = 1 / (1 - p)
   // saving form (hand kernel only): the pairs are walked in the backward's blocks and the kernel leaves q / y records (common.h:
   // PB_REC_BYTES) and x = SiLU(a_i + b_j) in block-row order for peneo_pair_bwd_saved; NULL = the plain walk, nothing saved
-  char* act; bf16_t* x_save; int ntiles;
+  // length-aware walk (peneo_pair_heads_fwd_lens; the LENS instantiations only, which save nothing): [B] token counts, clamped to
+  // [0, N] by the kernel; document b is walked as the n_b-token document it is, everything indexed by the pair keeps the N-packed
+  // index.  It shares the slot of x_save (which of the two the slot holds is the launcher's `lens_walk` argument, not a field):
+  // the kernel arguments of every other instantiation keep their size and offsets
+  char* act; union { bf16_t* x_save; const int32_t* lens; }; int ntiles;
   int act_e4m3;      // the records are the 1 KiB e4m3 form (common.h: PB_REC8_BYTES; peneo_pair_heads_fwd_save_e4m3)
 };
+static_assert(sizeof(PairFwdParams) == 400, "kernel-argument layout of the pair-head forward kernels");
+
+// the LENS walk: n_b, and what a workgroup without a live pair does before it leaves (peneo_loss_finish reads every row)
+__device__ __forceinline__ int pair_lens_doc(const PairFwdParams& p, int b) { return min(max(p.lens[b], 0), p.N); }
+__device__ __forceinline__ void pair_lens_zero_row(const PairFwdParams& p, int b, int tid) {
+  if (p.partials && tid < 32) p.partials[((int64_t)b * gridDim.x + blockIdx.x) * 32 + tid] = 0.f;
+}
 
 constexpr float NEG_INF_F = -3.0e38f;
 // register arrays must only ever be indexed by compile-time constants (dynamic indices go to scratch)
@@ -136,7 +147,7 @@ __device__ __forceinline__ void pair_epilogue_t(const PairFwdParams& p, const f3
 // at a stride of a whole number of 4 KiB: one 1 KiB DMA piece per wave of the four-wave workgroup and round.
 __host__ __device__ inline int64_t pair_wide_slab_bytes(int D) { return (int64_t)((D / 16 + 2 + 3) / 4) * 4096; }
 bool pair_wide_supported(int dtype, int D, int num_heads);
-int pair_wide_fwd(const PairFwdParams& p, hipStream_t st);
+int pair_wide_fwd(const PairFwdParams& p, hipStream_t st, bool lens_walk = false);   // lens_walk: peneo_pair_heads_fwd_lens (p.lens set)
 
 // peneo_pair_dz_fused: the launch parameters of pair_dz_fused_kernel (pair_heads.hip: D <= 512, eight waves) and of
 // pair_dz_wide_kernel (pair_dz_wide.hip: 512 < D <= 1024, four waves, the packed image and slab stride of the wide forward).

@@ -199,8 +199,10 @@ __device__ __forceinline__ void pair_epilogue(const PairFwdParams& p, const f32x
 //   1: LDS-DMA issued from inline asm with counted vmcnt (else the builtin, which hipcc drains before every ds_read)
 //   2: bias + SiLU + second layer of slab s-1 software-pipelined into the first-layer MFMA stream of slab s
 //   4: two independent first-layer accumulator chains (even / odd k-steps)
-template <typename T, int KS, int NSTAGE, int VARIANT, bool DROP>
+// LENS (peneo_pair_heads_fwd_lens, no dropout): the workgroup's 256 pairs are local pairs of the n_b-token document (pair_heads.h)
+template <typename T, int KS, int NSTAGE, int VARIANT, bool DROP, bool LENS = false>
 __global__ __launch_bounds__(PH_WAVES * 64, sizeof(T) == 2 ? (PH_WAVES > 8 ? 3 : 2) : 1) void pair_heads_fwd_kernel(PairFwdParams p) {
+  static_assert(!LENS || !DROP, "the length-aware walk is an inference form");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr bool ASM_DMA = (VARIANT & 1) != 0, PIPE_EPI = (VARIANT & 2) != 0, DUAL = (VARIANT & 4) != 0;
   constexpr bool SGB = (VARIANT & 16) != 0;       // sched_group_barrier interleave: 1 MFMA : 1 ds_read : few VALU
@@ -219,10 +221,18 @@ __global__ __launch_bounds__(PH_WAVES * 64, sizeof(T) == 2 ? (PH_WAVES > 8 ? 3 :
   const int D = p.D, N = p.N;
   const int b = blockIdx.y;
   const int64_t p0 = (int64_t)blockIdx.x * PH_PAIRS;
-  const int64_t mypair = p0 + wave * 32 + (lane & 31);
-  const bool pair_ok = mypair < p.P;
+  int64_t mypair = p0 + wave * 32 + (lane & 31);
+  int nb = N;
+  int64_t Pb = p.P;
+  if constexpr (LENS) {
+    nb = pair_lens_doc(p, b);
+    Pb = (int64_t)nb * (nb + 1) / 2;
+    if (p0 >= Pb) { pair_lens_zero_row(p, b, tid); return; }   // (uniform over the workgroup; before any barrier or DMA)
+  }
+  const bool pair_ok = mypair < Pb;
   int pi, pj;
-  pair_decode(pair_ok ? mypair : p.P - 1, N, pi, pj);
+  pair_decode(pair_ok ? mypair : Pb - 1, nb, pi, pj);
+  if constexpr (LENS) { mypair = pair_row_start(pi, N) + (pj - pi); asm volatile("" : "+v"(mypair)); }   // what the epilogue indexes by (made here)
   const int nslab = p.num_heads * D / 32;
 
   for (int i = tid; i < p.num_heads * D; i += PH_WAVES * 64) sB1[i] = p.b1[i];
@@ -783,9 +793,11 @@ template <int N, int I = 0, typename F> __device__ __forceinline__ void ph_stati
 
 // E4M3 (with SAVE): the records are the 1 KiB e4m3 form of common.h (PB_REC8_BYTES) instead of the 2 KiB f16 form; the walk, the
 // arithmetic and everything else the kernel writes are the same statements
-template <int KS, bool DROP, bool SAVE, bool E4M3 = false>
+// LENS (peneo_pair_heads_fwd_lens; plain walk, no dropout): as in the generic kernel
+template <int KS, bool DROP, bool SAVE, bool E4M3 = false, bool LENS = false>
 __global__ __launch_bounds__(PH_WAVES * 64, 2) void pair_heads_fwd_hand_kernel(PairFwdParams p) {
   static_assert(SAVE || !E4M3, "the e4m3 records are a form of the saving walk");
+  static_assert(!LENS || (!DROP && !SAVE), "the length-aware walk is an inference form of the plain walk");
   using T = bf16_t;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int NF = KS + 2;
@@ -821,8 +833,16 @@ __global__ __launch_bounds__(PH_WAVES * 64, 2) void pair_heads_fwd_hand_kernel(P
   } else {
     const int64_t p0 = (int64_t)blockIdx.x * PH_PAIRS;
     mypair = p0 + wave * 32 + (lane & 31);
-    pair_ok = mypair < p.P;
-    pair_decode(pair_ok ? mypair : p.P - 1, N, pi, pj);
+    int nb = N;
+    int64_t Pb = p.P;
+    if constexpr (LENS) {
+      nb = pair_lens_doc(p, b);
+      Pb = (int64_t)nb * (nb + 1) / 2;
+      if (p0 >= Pb) { pair_lens_zero_row(p, b, tid); return; }   // (uniform over the workgroup; before any barrier or DMA)
+    }
+    pair_ok = mypair < Pb;
+    pair_decode(pair_ok ? mypair : Pb - 1, nb, pi, pj);
+    if constexpr (LENS) { mypair = pair_row_start(pi, N) + (pj - pi); asm volatile("" : "+v"(mypair)); }   // what the epilogue indexes by (made here)
   }
   const int nslab = p.num_heads * D / 32;
 
@@ -1130,30 +1150,31 @@ __global__ __launch_bounds__(PH_WAVES * 64, 2) void pair_heads_fwd_hand_kernel(P
   pair_epilogue(p, lg, smem, tid, lane, wave, half, b, mypair, pair_ok);
 }
 
-template <int KS, bool DROP, bool SAVE, bool E4M3 = false>
+template <int KS, bool DROP, bool SAVE, bool E4M3 = false, bool LENS = false>
 static int launch_pair_fwd_hand(const PairFwdParams& p, hipStream_t st) {
-  constexpr const char* who = E4M3 ? "peneo_pair_heads_fwd_save_e4m3" : "peneo_pair_heads_fwd";
+  constexpr const char* who = LENS ? "peneo_pair_heads_fwd_lens" : E4M3 ? "peneo_pair_heads_fwd_save_e4m3" : "peneo_pair_heads_fwd";
   const size_t slab = (size_t)slab_stride_bytes(KS * 16, 2);
   const size_t nstage = 4 * slab + 5 * 512 * 4 <= 160 * 1024 ? 4 : 3;      // as in the kernel
   size_t sh = nstage * slab + (size_t)p.num_heads * p.D * sizeof(float);
   if (sh > 160 * 1024) { set_error("%s: D=%d needs %zu bytes of LDS", who, p.D, sh); return PENEO_ERR_INVALID; }
-  if (raise_dynamic_lds(pair_heads_fwd_hand_kernel<KS, DROP, SAVE, E4M3>, sh, who) != PENEO_OK) return PENEO_ERR_LAUNCH;
+  if (raise_dynamic_lds(pair_heads_fwd_hand_kernel<KS, DROP, SAVE, E4M3, LENS>, sh, who) != PENEO_OK) return PENEO_ERR_LAUNCH;
   dim3 grid(SAVE ? (unsigned)((p.ntiles + 1) / 2) : (unsigned)((p.P + PH_PAIRS - 1) / PH_PAIRS), p.B);
-  hipLaunchKernelGGL((pair_heads_fwd_hand_kernel<KS, DROP, SAVE, E4M3>), grid, dim3(PH_WAVES * 64), sh, st, p);
+  hipLaunchKernelGGL((pair_heads_fwd_hand_kernel<KS, DROP, SAVE, E4M3, LENS>), grid, dim3(PH_WAVES * 64), sh, st, p);
   return check_launch(who);
 }
 
-template <typename T, int KS, int VARIANT, bool DROP>
+template <typename T, int KS, int VARIANT, bool DROP, bool LENS = false>
 static int launch_pair_fwd_v(const PairFwdParams& p, hipStream_t st) {
+  constexpr const char* who = LENS ? "peneo_pair_heads_fwd_lens" : "peneo_pair_heads_fwd";
   constexpr int NSTAGE = (VARIANT & 128) ? 4 : (sizeof(T) == 2 ? 3 : 2);
   const size_t slab = (size_t)slab_stride_bytes(KS * 16, (int)sizeof(T));
   size_t sh = NSTAGE * slab + (size_t)p.num_heads * p.D * sizeof(float);
   if (sh < (size_t)PH_WAVES * 32 * sizeof(float)) sh = (size_t)PH_WAVES * 32 * sizeof(float);
-  if (sh > 160 * 1024) { set_error("peneo_pair_heads_fwd: D=%d needs %zu bytes of LDS", p.D, sh); return PENEO_ERR_INVALID; }
-  if (sh > 64 * 1024 && raise_dynamic_lds(pair_heads_fwd_kernel<T, KS, NSTAGE, VARIANT, DROP>, sh, "peneo_pair_heads_fwd") != PENEO_OK) return PENEO_ERR_LAUNCH;
+  if (sh > 160 * 1024) { set_error("%s: D=%d needs %zu bytes of LDS", who, p.D, sh); return PENEO_ERR_INVALID; }
+  if (sh > 64 * 1024 && raise_dynamic_lds(pair_heads_fwd_kernel<T, KS, NSTAGE, VARIANT, DROP, LENS>, sh, who) != PENEO_OK) return PENEO_ERR_LAUNCH;
   dim3 grid((unsigned)((p.P + PH_PAIRS - 1) / PH_PAIRS), p.B);
-  hipLaunchKernelGGL((pair_heads_fwd_kernel<T, KS, NSTAGE, VARIANT, DROP>), grid, dim3(PH_WAVES * 64), sh, st, p);
-  return check_launch("peneo_pair_heads_fwd");
+  hipLaunchKernelGGL((pair_heads_fwd_kernel<T, KS, NSTAGE, VARIANT, DROP, LENS>), grid, dim3(PH_WAVES * 64), sh, st, p);
+  return check_launch(who);
 }
 
 // bf16: LDS-DMA from inline asm with counted vmcnt (variant 1): 1761 us against 1838 us for the builtin at B = 8
@@ -1162,8 +1183,15 @@ constexpr int PH_DEFAULT_VARIANT = 1;
 // tools/: PENEO_PAIR_FWD_HAND=0 selects the generic kernel at D = 384 / 512 too
 static bool pair_fwd_hand() { static const bool v = env_switch_on("PENEO_PAIR_FWD_HAND"); return v; }
 template <typename T, int KS>
-static int launch_pair_fwd(const PairFwdParams& p, hipStream_t st) {
+static int launch_pair_fwd(const PairFwdParams& p, hipStream_t st, bool lens_walk) {
   constexpr int V = sizeof(T) == 2 ? PH_DEFAULT_VARIANT : 0;
+  if (lens_walk) {
+    // peneo_pair_heads_fwd_lens (no dropout, nothing saved): the LENS form of the kernel the plain call would take
+    if constexpr (sizeof(T) == 2 && (KS == 24 || KS == 32)) {
+      if (pair_fwd_hand() && p.num_heads * p.D / 32 >= 2) return launch_pair_fwd_hand<KS, false, false, false, true>(p, st);
+    }
+    return launch_pair_fwd_v<T, KS, V, false, true>(p, st);
+  }
   if constexpr (sizeof(T) == 2 && (KS == 24 || KS == 32)) {
     if constexpr (KS == 24) {
       if (p.act && p.act_e4m3 && p.num_heads * p.D / 32 >= 2)
@@ -1179,22 +1207,22 @@ static int launch_pair_fwd(const PairFwdParams& p, hipStream_t st) {
 }
 
 template <typename T>
-static int dispatch_pair_fwd(const PairFwdParams& p, hipStream_t st) {
+static int dispatch_pair_fwd(const PairFwdParams& p, hipStream_t st, bool lens_walk = false) {   // lens_walk: p.lens is set (pair_heads.h)
   if (p.D > 512) {
     // pair_heads_wide.hip: bf16 on four waves with the whole register file each; nothing for fp32 (its x fragments are twice as large)
-    if (sizeof(T) == 2 && !p.act && pair_wide_supported(PENEO_BF16, p.D, p.num_heads)) return pair_wide_fwd(p, st);
+    if (sizeof(T) == 2 && !p.act && pair_wide_supported(PENEO_BF16, p.D, p.num_heads)) return pair_wide_fwd(p, st, lens_walk);
     set_error("peneo_pair_heads_fwd: D=%d not supported (above 512: bf16 only, D a multiple of 64 up to 1024, no saving form)", p.D);
     return PENEO_ERR_INVALID;
   }
   switch (p.D / 16) {
-    case 2: return launch_pair_fwd<T, 2>(p, st);
-    case 4: return launch_pair_fwd<T, 4>(p, st);
-    case 6: return launch_pair_fwd<T, 6>(p, st);
-    case 8: return launch_pair_fwd<T, 8>(p, st);
-    case 12: return launch_pair_fwd<T, 12>(p, st);
-    case 16: return launch_pair_fwd<T, 16>(p, st);
-    case 24: return launch_pair_fwd<T, 24>(p, st);
-    case 32: return launch_pair_fwd<T, 32>(p, st);
+    case 2: return launch_pair_fwd<T, 2>(p, st, lens_walk);
+    case 4: return launch_pair_fwd<T, 4>(p, st, lens_walk);
+    case 6: return launch_pair_fwd<T, 6>(p, st, lens_walk);
+    case 8: return launch_pair_fwd<T, 8>(p, st, lens_walk);
+    case 12: return launch_pair_fwd<T, 12>(p, st, lens_walk);
+    case 16: return launch_pair_fwd<T, 16>(p, st, lens_walk);
+    case 24: return launch_pair_fwd<T, 24>(p, st, lens_walk);
+    case 32: return launch_pair_fwd<T, 32>(p, st, lens_walk);
     default: set_error("peneo_pair_heads_fwd: D=%d not supported (D/16 in {2,4,6,8,12,16,24,32})", p.D); return PENEO_ERR_INVALID;
   }
 }
@@ -1560,11 +1588,46 @@ extern "C" int peneo_pair_heads_pack(int dtype, const float* const* w1, const fl
   return check_launch("peneo_pair_heads_pack");
 }
 
+// peneo_pair_heads_fwd_lens: the background row (class 0 = 0, every other class = PENEO_PAIR_PAD_LOGIT) of every pair that touches the
+// padding of its document.  Block = (row i of the triangle, document): the pairs (i, j >= max(i, n_b)) are one contiguous run of the
+// N-packed maps, so nothing is decoded; a row without such a pair (n_b = N) costs its block one load.  The pairs the main kernel
+// writes (j < n_b) are the others: the two launches never meet on an element.
+__global__ __launch_bounds__(256) void pair_pad_fill_kernel(PairFwdParams p) {
+  const int i = blockIdx.x, b = blockIdx.y, N = p.N;
+  const int nb = pair_lens_doc(p, b);
+  const int64_t row = (int64_t)b * p.P + pair_row_start(i, N) - i;
+  for (int j = max(i, nb) + (int)threadIdx.x; j < N; j += 256) {
+#pragma unroll
+    for (int h = 0; h < PENEO_MAX_HEADS; ++h) {
+      if (h < p.num_heads && p.logits[h]) {
+        const int C = p.classes[h];
+        float* dst = p.logits[h] + (row + j) * C;
+        for (int c = 0; c < C; ++c) dst[c] = c == 0 ? 0.f : PENEO_PAIR_PAD_LOGIT;
+      }
+    }
+  }
+}
+
+// n_b = 1 + the last index of row b whose mask is non-zero (0: none; N: no mask).  One workgroup a document
+__global__ __launch_bounds__(256) void pair_lens_from_mask_kernel(const int64_t* mask, int64_t ld, int N, int32_t* lens) {
+  __shared__ int red[4];
+  const int b = blockIdx.x;
+  int last = mask ? 0 : N;
+  if (mask)
+    for (int j = threadIdx.x; j < N; j += 256)
+      if (mask[(int64_t)b * ld + j] != 0) last = j + 1;   // (j increases: the thread's last hit is its largest)
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) last = max(last, __shfl_xor(last, o, 64));
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = last;
+  __syncthreads();
+  if (threadIdx.x == 0) lens[b] = max(max(red[0], red[1]), max(red[2], red[3]));
+}
+
 static int pair_heads_fwd_impl(int dtype, const void* ab, int B, int N, const peneo_pair_heads_desc* desc,
                                float* const* logits, const peneo_pair_loss* loss, void* act, void* x_rows, peneo_stream_t stream,
-                               bool act_e4m3 = false) {
+                               bool act_e4m3 = false, const int32_t* lens = nullptr) {
   // the entry point the error texts name (the f16 saving form has always reported as peneo_pair_heads_fwd / _save)
-  const char* const who = act_e4m3 ? "peneo_pair_heads_fwd_save_e4m3" : "peneo_pair_heads_fwd";
+  const char* const who = lens ? "peneo_pair_heads_fwd_lens" : act_e4m3 ? "peneo_pair_heads_fwd_save_e4m3" : "peneo_pair_heads_fwd";
   const char* const who_save = act_e4m3 ? "peneo_pair_heads_fwd_save_e4m3" : "peneo_pair_heads_fwd_save";
   PENEO_REQUIRE(ok_dt(dtype) && ab && desc && B > 0 && N > 0, "%s: bad arguments", who);
   PENEO_REQUIRE(desc->num_heads > 0 && desc->num_heads <= PENEO_MAX_HEADS, "%s: num_heads out of range", who);
@@ -1599,12 +1662,47 @@ static int pair_heads_fwd_impl(int dtype, const void* ab, int B, int N, const pe
     p.act = static_cast<char*>(act); p.x_save = static_cast<bf16_t*>(x_rows); p.ntiles = pb_num_tiles(N);
     p.act_e4m3 = act_e4m3 ? 1 : 0;
   }
-  return dtype == PENEO_BF16 ? dispatch_pair_fwd<bf16_t>(p, (hipStream_t)stream) : dispatch_pair_fwd<float>(p, (hipStream_t)stream);
+  if (lens) {
+    // (every refusal of the dispatch below has been made by peneo_pair_heads_fwd_lens: nothing is launched for a call that fails)
+    p.lens = lens;                                      // (act is NULL here: the slot of x_save is free)
+    bool any = false;
+    for (int h = 0; h < desc->num_heads; ++h) any = any || p.logits[h];
+    if (any) {
+      PENEO_REQUIRE(B <= 65535, "%s: B=%d exceeds the grid of the padding fill", who, B);
+      hipLaunchKernelGGL(pair_pad_fill_kernel, dim3((unsigned)N, (unsigned)B), dim3(256), 0, (hipStream_t)stream, p);
+      const int rc = check_launch(who);
+      if (rc != PENEO_OK) return rc;
+    }
+  }
+  return dtype == PENEO_BF16 ? dispatch_pair_fwd<bf16_t>(p, (hipStream_t)stream, lens != nullptr)
+                             : dispatch_pair_fwd<float>(p, (hipStream_t)stream, lens != nullptr);
 }
 
 extern "C" int peneo_pair_heads_fwd(int dtype, const void* ab, int B, int N, const peneo_pair_heads_desc* desc,
                                     float* const* logits, const peneo_pair_loss* loss, peneo_stream_t stream) {
   return pair_heads_fwd_impl(dtype, ab, B, N, desc, logits, loss, nullptr, nullptr, stream);
+}
+
+extern "C" int peneo_pair_lens_from_mask(const int64_t* mask, int64_t ld, int B, int N, int32_t* lens, peneo_stream_t stream) {
+  PENEO_REQUIRE(lens && B > 0 && N > 0, "peneo_pair_lens_from_mask: bad arguments");
+  PENEO_REQUIRE(!mask || ld >= N, "peneo_pair_lens_from_mask: row stride %lld below N=%d", (long long)ld, N);
+  hipLaunchKernelGGL(pair_lens_from_mask_kernel, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, mask, ld, N, lens);
+  return check_launch("peneo_pair_lens_from_mask");
+}
+
+extern "C" int peneo_pair_heads_fwd_lens(int dtype, const void* ab, int B, int N, const int32_t* lens,
+                                         const peneo_pair_heads_desc* desc, float* const* logits, const peneo_pair_loss* loss,
+                                         peneo_stream_t stream) {
+  const char* const who = "peneo_pair_heads_fwd_lens";
+  PENEO_REQUIRE(lens, "%s: null lens", who);
+  PENEO_REQUIRE(ok_dt(dtype) && ab && desc && B > 0 && N > 0, "%s: bad arguments", who);
+  PENEO_REQUIRE(desc->drop_p == 0.f, "%s: an inference entry point, drop_p must be 0 (got %g)", who, (double)desc->drop_p);
+  if (loss)
+    for (int h = 0; h < PENEO_MAX_HEADS; ++h)
+      PENEO_REQUIRE(!loss->dlogits[h], "%s: an inference entry point, loss->dlogits[%d] must be NULL", who, h);
+  PENEO_REQUIRE(peneo_pair_heads_supported(dtype, desc->D, desc->num_heads),
+                "%s: no kernel for dtype %d, D=%d, %d heads (peneo_pair_heads_supported)", who, dtype, desc->D, desc->num_heads);
+  return pair_heads_fwd_impl(dtype, ab, B, N, desc, logits, loss, nullptr, nullptr, stream, false, lens);
 }
 
 extern "C" int peneo_pair_save_supported(int dtype, int D, int num_heads) {

@@ -25,8 +25,10 @@ constexpr int PW_WAVES = 4;
 constexpr int PW_ROUND = PW_WAVES * 32;    // pairs per round
 constexpr int PW_PAIRS = 2 * PW_ROUND;     // pairs per workgroup == pairs per row of loss partials (pair_heads.hip: PH_PAIRS)
 
-template <int KS, bool DROP>
+// LENS (peneo_pair_heads_fwd_lens, no dropout): the workgroup's 256 pairs are local pairs of the n_b-token document (pair_heads.h)
+template <int KS, bool DROP, bool LENS = false>
 __global__ __launch_bounds__(PW_WAVES * 64, 1) void pair_heads_wide_kernel(PairFwdParams p) {
+  static_assert(!LENS || !DROP, "the length-aware walk is an inference form");
   using T = bf16_t;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int UPW = (KS + 2 + PW_WAVES - 1) / PW_WAVES;   // 1 KiB DMA pieces per wave per slab
@@ -40,6 +42,14 @@ __global__ __launch_bounds__(PW_WAVES * 64, 1) void pair_heads_wide_kernel(PairF
   const int b = blockIdx.y;
   const int nslab = p.num_heads * D / 32;
   const T* abd = reinterpret_cast<const T*>(p.ab) + (int64_t)b * N * 2 * D;
+  [[maybe_unused]] int nb = 0;
+  [[maybe_unused]] int64_t Pb = 0;
+  if constexpr (LENS) {
+    nb = pair_lens_doc(p, b);
+    Pb = (int64_t)nb * (nb + 1) / 2;
+    // (uniform over the workgroup; before any barrier or DMA)
+    if ((int64_t)blockIdx.x * PW_PAIRS >= Pb) { pair_lens_zero_row(p, b, tid); return; }
+  }
 
   for (int i = tid; i < p.num_heads * D; i += PW_WAVES * 64) sB1[i] = p.b1[i];
 
@@ -50,11 +60,16 @@ __global__ __launch_bounds__(PW_WAVES * 64, 1) void pair_heads_wide_kernel(PairF
 
   for (int round = 0; round < 2; ++round) {
     const int64_t p0 = (int64_t)blockIdx.x * PW_PAIRS + round * PW_ROUND;
-    if (p0 >= p.P) break;                                   // (uniform over the workgroup)
-    const int64_t mypair = p0 + wave * 32 + (lane & 31);
-    const bool pair_ok = mypair < p.P;
+    // (LENS is a constant: the plain instantiations keep their statements, each where it stood - this kernel is compiler-scheduled,
+    // and a reordered form of the same walk came out 300 to 750 instructions longer per kernel)
+    if (p0 >= (LENS ? Pb : p.P)) break;                     // (uniform over the workgroup)
+    const int64_t qpair = p0 + wave * 32 + (lane & 31);     // the pair within the document as it is walked
+    const bool pair_ok = qpair < (LENS ? Pb : p.P);
     int pi, pj;
-    pair_decode(pair_ok ? mypair : p.P - 1, N, pi, pj);
+    pair_decode(pair_ok ? qpair : (LENS ? Pb : p.P) - 1, LENS ? nb : N, pi, pj);
+    int64_t packed = qpair;                                 // what the epilogue indexes by: N-packed
+    if constexpr (LENS) { packed = pair_row_start(pi, N) + (pj - pi); asm volatile("" : "+v"(packed)); }   // (made here, not later)
+    const int64_t mypair = packed;
 
     // ---- x = SiLU(a_i + b_j) as B-operand fragments (k = decoder dim), kept in registers ----
     const T* arow = abd + (int64_t)pi * 2 * D;
@@ -151,22 +166,24 @@ bool pair_wide_supported(int dtype, int D, int num_heads) {
          pair_wide_lds_bytes(D, num_heads) <= 160 * 1024;
 }
 
-template <int KS, bool DROP>
+template <int KS, bool DROP, bool LENS = false>
 static int launch_pair_wide(const PairFwdParams& p, hipStream_t st) {
+  constexpr const char* who = LENS ? "peneo_pair_heads_fwd_lens" : "peneo_pair_heads_fwd";
   const size_t sh = pair_wide_lds_bytes(p.D, p.num_heads);
-  if (raise_dynamic_lds(pair_heads_wide_kernel<KS, DROP>, sh, "peneo_pair_heads_fwd") != PENEO_OK) return PENEO_ERR_LAUNCH;
+  if (raise_dynamic_lds(pair_heads_wide_kernel<KS, DROP, LENS>, sh, who) != PENEO_OK) return PENEO_ERR_LAUNCH;
   dim3 grid((unsigned)((p.P + PW_PAIRS - 1) / PW_PAIRS), p.B);
-  hipLaunchKernelGGL((pair_heads_wide_kernel<KS, DROP>), grid, dim3(PW_WAVES * 64), sh, st, p);
-  return check_launch("peneo_pair_heads_fwd");
+  hipLaunchKernelGGL((pair_heads_wide_kernel<KS, DROP, LENS>), grid, dim3(PW_WAVES * 64), sh, st, p);
+  return check_launch(who);
 }
 
-int pair_wide_fwd(const PairFwdParams& p, hipStream_t st) {
+int pair_wide_fwd(const PairFwdParams& p, hipStream_t st, bool lens_walk) {
   if (!pair_wide_supported(PENEO_BF16, p.D, p.num_heads) || p.act) {
     set_error("peneo_pair_heads_fwd: D=%d with %d heads not supported by the wide kernel", p.D, p.num_heads);
     return PENEO_ERR_INVALID;
   }
+  // (lens_walk: peneo_pair_heads_fwd_lens, which has refused dropout)
 #define PENEO_PW_CASE(KS_) \
-  case KS_: return p.drop_thr16 ? launch_pair_wide<KS_, true>(p, st) : launch_pair_wide<KS_, false>(p, st);
+  case KS_: return lens_walk ? launch_pair_wide<KS_, false, true>(p, st) : p.drop_thr16 ? launch_pair_wide<KS_, true>(p, st) : launch_pair_wide<KS_, false>(p, st);
   switch (p.D / 16) {
     PENEO_PW_CASE(36) PENEO_PW_CASE(40) PENEO_PW_CASE(44) PENEO_PW_CASE(48)
     PENEO_PW_CASE(52) PENEO_PW_CASE(56) PENEO_PW_CASE(60) PENEO_PW_CASE(64)

@@ -200,6 +200,15 @@ class PEneoModel(PEneoPreTrainedModel):
         self.peneo_decoder.set_pair_act_format(fmt, self._compute_dtype)
         return self
 
+    def set_skip_padded_pairs(self, on: bool) -> "PEneoModel":
+        """Opt-in inference switch (default off; PENEO_SKIP_PADDED_PAIRS=1 turns it on at construction): forwards that need no
+        gradients and receive an ``attention_mask`` score only the pairs of real tokens (PEneoDecoder.set_skip_padded_pairs).  The
+        maps keep their shape; pairs that touch the padding decode to nothing, and the returned losses are live-pair losses, not the
+        reference's means over all pairs.  Forwards with gradients and forwards without a mask are unchanged.  Not together with
+        set_pair_heads_format("mxfp8"): ValueError."""
+        self.peneo_decoder.set_skip_padded_pairs(on)
+        return self
+
     def set_encoder_format(self, fmt: str) -> "PEneoModel":
         """"bf16" (default) or "mxfp8": the MXFP8 inference path of the backbone's encoder layers (LayoutLMv3Model.set_encoder_format;
         eval forwards without gradients only).  Independent of set_pair_heads_format.  "mxfp8" needs compute dtype torch.bfloat16 and

@@ -139,6 +139,10 @@ class HandshakingTaggingScheme:
 
 @dataclass
 class PEneoOutput(ModelOutput):
+    """The reference's output record.  Of a forward that ran with ``skip_padded_pairs`` (PEneoDecoder.set_skip_padded_pairs: no
+    gradients, an attention mask given) the six losses are LIVE-PAIR losses - class-weighted means over the pairs of real tokens,
+    not over all P pairs as the reference's - and the ``*_shaking_outputs`` hold (0, -1e30, ...) at every pair that touches the
+    padding."""
     loss: Optional[torch.Tensor] = None
 
     line_extraction_loss: Optional[torch.Tensor] = None
@@ -207,11 +211,14 @@ class PairRoute:
     backward: Optional[str] = None   # "generic" | "saved" | "fused" | "chunked"; None: nothing to run (no gradients or no labels)
     dz: Optional[str] = None         # "chunked" only, its dz producer: "fused" | "wide" | "epilogue" | "standalone"
     writes_x: bool = False           # "wide" only: that kernel also stores x / a_i + b_j (no peneo_pair_x_fwd launch)
+    lens: bool = False               # "bf16" without gradients only: the length-aware launch (peneo_pair_heads_fwd_lens)
 
 
-def pair_route(dec: "PEneoDecoder", dt: torch.dtype, D: int, need_grad: bool, has_tags: bool, p_hidden: float) -> PairRoute:
+def pair_route(dec: "PEneoDecoder", dt: torch.dtype, D: int, need_grad: bool, has_tags: bool, p_hidden: float,
+               has_mask: bool = False) -> PairRoute:
     """The route of a step at compute dtype `dt` and decoder width `D` from the decoder's switches and formats and the
-    library's host-side queries (no GPU).  p_hidden: the classifier dropout in force (DropoutSeeds.p_hidden)."""
+    library's host-side queries (no GPU).  p_hidden: the classifier dropout in force (DropoutSeeds.p_hidden).  has_mask: the
+    forward received an attention mask (what skip_padded_pairs takes the lengths from)."""
     nh = len(HEAD_NAMES)
     train = need_grad and has_tags
     if not dec.fused_pair_heads(dt, D):
@@ -220,7 +227,10 @@ def pair_route(dec: "PEneoDecoder", dt: torch.dtype, D: int, need_grad: bool, ha
     if dec.pair_heads_format == "mxfp8":
         return PairRoute("mxfp8_eval")   # (PEneoDecoder.forward has refused a forward with gradients)
     if not train:
-        return PairRoute("bf16")
+        # skip_padded_pairs: forwards without gradients only (a forward with gradients and no labels stays today's too); OHEM picks
+        # its pairs from the finished maps, padding included, and keeps the plain launch
+        lens = dec.skip_padded_pairs and has_mask and not need_grad and not (has_tags and dec.le_loss.ohem)
+        return PairRoute("bf16", lens=True) if lens else PairRoute("bf16")
     if dec.fused_bwd and ops.pair_bwd_supported(dt, D, nh):   # (LDS: the head count enters, D = 512 holds 5 heads)
         # the forward of such a step leaves the classifiers' pre-activations (dropout applied) and x in the backward's block order, 2
         # bytes per pair and hidden unit (4.2 GB at 8 x 511 tokens): the backward repeats neither the first-layer product nor the mask
@@ -274,12 +284,13 @@ class _DecoderStage(torch.autograd.Function):
     forward and kept in ``saved["route"]`` (as run: without the saved form where its buffers did not fit)."""
 
     @staticmethod
-    def forward(ctx, dec, seq, B, N, tags, want_logits, need_grad, *params):
+    def forward(ctx, dec, seq, B, N, tags, want_logits, need_grad, mask, *params):
         wc, dt, dev = dec.weight_cache, seq.dtype, seq.device
         sp = _stage_params(dec, params)
         D = sp.wc_w.shape[0]
         # (DropoutSeeds.p_hidden, before the seeds are drawn: a refused step does not advance them)
-        route = pair_route(dec, dt, D, need_grad, tags is not None, float(dec.dropout_p) if dec.training else 0.0)
+        route = pair_route(dec, dt, D, need_grad, tags is not None, float(dec.dropout_p) if dec.training else 0.0,
+                           has_mask=mask is not None)
         # strict deterministic mode: say which piece of this step has no order-independent backward, before any of it runs
         what = strict_refusal(dec, route, dt, D) if need_grad and tags is not None and deterministic_mode() == 2 else None
         if what:
@@ -347,6 +358,13 @@ class _DecoderStage(torch.autograd.Function):
             return _DecoderStage._finish(ctx, res, tags, cws)
         wp = wc.get(("dec.pack", dt), w1s + w2s, lambda: ops.pair_heads_pack(dt, [w.detach() for w in w1s],
                                                                              [w.detach() for w in w2s]))
+        if route.lens:
+            # skip_padded_pairs: the lengths from the cropped mask, on the device (no synchronisation); pairs that touch the padding
+            # get the background row, the losses are those of the live pairs
+            assert not need_grad and seeds.p_hidden == 0.0
+            res = ops.pair_heads_fwd_lens(ab, ops.pair_lens_from_mask(mask, N), wp, b1cat, b2cat, HEAD_CLASSES,
+                                          want_logits=want_logits, tags=tags, class_weights=cws)
+            return _DecoderStage._finish(ctx, res, tags, cws)
         res = ops.pair_heads_fwd(ab, wp, b1cat, b2cat, HEAD_CLASSES, want_logits=want_logits,
                                  tags=tags, class_weights=cws, want_dlogits=need_grad and tags is not None,
                                  drop_p=seeds.p_hidden, drop_seed=seeds.seed(903), save=route.save, save_buffers=bufs,
@@ -641,7 +659,7 @@ class _DecoderStage(torch.autograd.Function):
                 defer_join(side, keep=keep, hold=can_hold)
             else:
                 torch.cuda.current_stream().wait_stream(side)
-        return (None, d_seq, None, None, None, None, None) + grads
+        return (None, d_seq, None, None, None, None, None, None) + grads
 
 
 def _generic_heads_forward(dec, ab, heads, tags, cws, seeds, need_grad, want_logits):
@@ -768,6 +786,8 @@ class PEneoDecoder(nn.Module):
         self.pair_heads_format = "bf16"   # set_pair_heads_format
         self.pair_heads_train_format = "bf16"   # set_pair_heads_train_format
         self.pair_act_format = "f16"            # set_pair_act_format
+        # forwards without gradients that received an attention mask skip the pairs touching the padding (set_skip_padded_pairs)
+        self.skip_padded_pairs = os.environ.get("PENEO_SKIP_PADDED_PAIRS", "0") == "1"
         self.handshaking_kernel = HandshakingKernel(D)
         self.inference_mode = config.inference_mode
 
@@ -830,7 +850,22 @@ class PEneoDecoder(nn.Module):
                 raise ValueError(f"mxfp8 pair heads need peneo_classifier_num_layers == 2, not {self.num_cls_layers}")
             if not ops.pair_mxfp8_supported(self.decoder_hidden_size, len(HEAD_NAMES)):
                 raise ValueError(f"mxfp8 pair heads do not support decoder width D = {self.decoder_hidden_size}")
+            if self.skip_padded_pairs:
+                raise ValueError("the mxfp8 pair heads have no length-aware form: switch set_skip_padded_pairs(False) first")
         self.pair_heads_format = fmt
+
+    def set_skip_padded_pairs(self, on: bool) -> None:
+        """False (default; PENEO_SKIP_PADDED_PAIRS=1 turns it on at construction): every forward scores all P = N (N + 1) / 2 pairs
+        of the padded sequence.  True: a forward that needs no gradients and received an ``attention_mask`` takes each document's
+        length from it (1 + the last non-zero position of the cropped mask) and runs the fused pair heads over the pairs of real
+        tokens only (peneo_pair_heads_fwd_lens).  The maps keep their [B, P, C] layout; a pair that touches the padding holds
+        (0, -1e30, ...), which decodes to nothing, and the returned losses are the LIVE-PAIR losses: class-weighted means over the
+        pairs of real tokens, not the reference's means over all P pairs.  Forwards with gradients (the training objective includes
+        the padded pairs), forwards without a mask, the materialising path (other classifier depths / widths) and OHEM losses are
+        exactly what they are with the switch off.  Not together with set_pair_heads_format("mxfp8"): ValueError."""
+        if on and self.pair_heads_format == "mxfp8":
+            raise ValueError("skip_padded_pairs has no mxfp8 form: switch back with set_pair_heads_format('bf16') first")
+        self.skip_padded_pairs = bool(on)
 
     def set_pair_heads_train_format(self, fmt: str, compute_dtype: torch.dtype = torch.bfloat16) -> None:
         """"bf16" (default): forwards with gradients run the pair heads in the compute dtype.  "mxfp8": a forward that needs
@@ -959,7 +994,11 @@ class PEneoDecoder(nn.Module):
             self._check_saved_format("mxfp8", sequence_output.dtype, "it cannot run with the e4m3 pair activations")
         if self.pair_act_format == "e4m3" and need_grad:
             self._check_saved_format("e4m3", sequence_output.dtype, "it cannot run with the e4m3 pair activations")
-        res = _DecoderStage.apply(self, sequence_output.reshape(B * N, Hin), B, N, tags, want_logits, need_grad, *params)
+        # (skip_padded_pairs: the cropped mask the model passes on; pair_route decides whether the step reads it)
+        mask = kwargs.get("attention_mask") if self.skip_padded_pairs else None
+        if mask is not None and tuple(mask.shape) != (B, N):
+            raise ValueError(f"skip_padded_pairs: attention_mask {tuple(mask.shape)} does not match the cropped sequence {(B, N)}")
+        res = _DecoderStage.apply(self, sequence_output.reshape(B * N, Hin), B, N, tags, want_logits, need_grad, mask, *params)
         loss, l_le, l_elh, l_elt, l_lgh, l_lgt, o_le, o_elh, o_elt, o_lgh, o_lgt = res
         if self.inference_mode:
             # NB the reference's tuple order differs from the dataclass field order (:365-373)

@@ -821,11 +821,12 @@ def pair_heads_pack(dtype: torch.dtype, w1: Sequence[torch.Tensor], w2: Sequence
 def _pair_heads_launch(entry: str, timer: str, ab: torch.Tensor, wp: torch.Tensor, b1: torch.Tensor, b2: torch.Tensor,
                        classes: Sequence[int], want_logits: bool, tags, class_weights, *, typed: bool = False,
                        want_dlogits: bool = False, drop_p: float = 0.0, drop_seed: int = 0, save_bytes: Optional[int] = None,
-                       save_buffers=None):
-    """The one launch behind pair_heads_fwd / pair_heads_fwd_mxfp8 / pair_heads_fwd_mxfp8_save: fills PairHeadsDesc and PairLoss,
-    allocates what the caller asked for and calls `entry` under kernel_timer(`timer`).  typed: the entry point takes the dtype
-    code first.  save_bytes: the entry point is a saving one - loss partials in the saving launch's rows, and (act [>= save_bytes]
-    uint8, x_rows) checked (save_buffers) or allocated, passed on and returned as a fourth value."""
+                       save_buffers=None, lens: Optional[torch.Tensor] = None, logits_out=None):
+    """The one launch behind pair_heads_fwd / pair_heads_fwd_lens / pair_heads_fwd_mxfp8 / pair_heads_fwd_mxfp8_save: fills
+    PairHeadsDesc and PairLoss, allocates what the caller asked for and calls `entry` under kernel_timer(`timer`).  typed: the entry
+    point takes the dtype code first.  save_bytes: the entry point is a saving one - loss partials in the saving launch's rows, and
+    (act [>= save_bytes] uint8, x_rows) checked (save_buffers) or allocated, passed on and returned as a fourth value.  lens: the
+    entry point takes the [B] int32 lengths after N.  logits_out: the caller's [B, P, C_h] fp32 maps instead of fresh ones."""
     B, N, D2 = ab.shape
     D = D2 // 2
     P = N * (N + 1) // 2
@@ -838,6 +839,11 @@ def _pair_heads_launch(entry: str, timer: str, ab: torch.Tensor, wp: torch.Tenso
     desc.w_packed, desc.b1, desc.b2 = ptr(wp), ptr(b1), ptr(b2)
     desc.drop_p, desc.drop_seed = float(drop_p), int(drop_seed) & 0xFFFFFFFF
     logits = [torch.empty((B, P, c), dtype=torch.float32, device=dev) for c in classes] if want_logits else None
+    if want_logits and logits_out is not None:
+        logits = list(logits_out)
+        for lg, c in zip(logits, classes):
+            assert lg.shape == (B, P, c) and lg.dtype == torch.float32 and lg.is_contiguous() and lg.device == dev
+        assert len(logits) == nh
     loss = partials = dlog = None
     if tags is not None:
         loss = hip.PairLoss()
@@ -853,7 +859,8 @@ def _pair_heads_launch(entry: str, timer: str, ab: torch.Tensor, wp: torch.Tenso
                 loss.dlogits[h] = ptr(dlog[h])
         loss.partials = ptr(partials)
     args = [dtype_code(ab.dtype)] if typed else []
-    args += [ptr(ab), B, N, C.byref(desc), _ptr_list(logits) if logits is not None else None, C.byref(loss) if loss is not None else None]
+    args += [ptr(ab), B, N] + ([ptr(lens)] if lens is not None else [])
+    args += [C.byref(desc), _ptr_list(logits) if logits is not None else None, C.byref(loss) if loss is not None else None]
     saved = ()
     if save_bytes is not None:
         if save_buffers is not None:
@@ -892,6 +899,49 @@ def pair_heads_fwd(ab: torch.Tensor, wp: torch.Tensor, b1: torch.Tensor, b2: tor
     return _pair_heads_launch(entry, "pair_heads_fwd", ab, wp, b1, b2, classes, want_logits, tags, class_weights, typed=True,
                               want_dlogits=want_dlogits, drop_p=drop_p, drop_seed=drop_seed, save_bytes=nbytes,
                               save_buffers=save_buffers)
+
+
+PAIR_PAD_LOGIT = -1e30                  # include/peneo_hip.h: PENEO_PAIR_PAD_LOGIT (as fp32: torch.tensor(-1e30, dtype=torch.float32))
+
+
+def pair_lens_from_mask(mask: Optional[torch.Tensor], N: int, *, B: Optional[int] = None, device=None) -> torch.Tensor:
+    """Token counts for pair_heads_fwd_lens from an attention mask [B, >= N] (any integer / bool dtype, on the device): int32 [B],
+    n_b = 1 + the last index below N whose mask is non-zero, 0 where there is none.  One launch, no host synchronisation.  mask None:
+    every length is N (B and device say how many, and where)."""
+    N = int(N)
+    if mask is None:
+        if B is None or device is None:
+            raise ValueError("pair_lens_from_mask: without a mask, B and device are needed")
+        lens = torch.empty(int(B), dtype=torch.int32, device=device)
+        check(lib().peneo_pair_lens_from_mask(None, 0, int(B), N, ptr(lens), stream()), "peneo_pair_lens_from_mask")
+        return lens
+    if mask.dim() != 2 or mask.shape[1] < N or not mask.is_cuda:
+        raise hip.PeneoHipError(f"pair_lens_from_mask: mask must be a device tensor [B, >= {N}], got {tuple(mask.shape)} on {mask.device}")
+    if mask.dtype != torch.int64:
+        mask = mask.to(torch.int64)
+    if mask.stride(1) != 1:
+        mask = mask.contiguous()
+    lens = torch.empty(mask.shape[0], dtype=torch.int32, device=mask.device)
+    check(lib().peneo_pair_lens_from_mask(ptr(mask), mask.stride(0), mask.shape[0], N, ptr(lens), stream()), "peneo_pair_lens_from_mask")
+    return lens
+
+
+def pair_heads_fwd_lens(ab: torch.Tensor, lens: torch.Tensor, wp: torch.Tensor, b1: torch.Tensor, b2: torch.Tensor,
+                        classes: Sequence[int], *, want_logits: bool = True, tags: Optional[Sequence[torch.Tensor]] = None,
+                        class_weights: Optional[Sequence[Optional[torch.Tensor]]] = None, logits_out=None):
+    """Length-aware inference form of pair_heads_fwd (include/peneo_hip.h: peneo_pair_heads_fwd_lens).  ab [B, N, 2D], wp from
+    pair_heads_pack, lens [B] int32 on ab's device (pair_lens_from_mask).  Returns (logits list | None, loss partials [n, 32] | None,
+    None) like pair_heads_fwd without dlogits: the logits of pairs with j < lens[b] are pair_heads_fwd's bit for bit, every other pair
+    holds (0, PAIR_PAD_LOGIT, ...); the partial rows sum over the live pairs only, so loss_finish over them is the class-weighted
+    mean over the pairs of real tokens, not the reference's mean over all P.  logits_out: caller-supplied maps to write into."""
+    _c(ab)
+    B = ab.shape[0]
+    if not torch.is_tensor(lens) or lens.dtype != torch.int32 or lens.device != ab.device or lens.shape != (B,) \
+            or not lens.is_contiguous():
+        what = f"{lens.dtype} {tuple(lens.shape)} on {lens.device}" if torch.is_tensor(lens) else type(lens).__name__
+        raise hip.PeneoHipError(f"pair_heads_fwd_lens: lens must be a contiguous int32 [{B}] tensor on {ab.device}, got {what}")
+    return _pair_heads_launch("peneo_pair_heads_fwd_lens", "pair_heads_fwd_lens", ab, wp, b1, b2, classes, want_logits, tags,
+                              class_weights, typed=True, lens=lens, logits_out=logits_out)
 
 
 PAIR_ACT_FORMATS = ("f16", "e4m3")      # record formats of the saved pair activations (include/peneo_hip.h)

@@ -68,7 +68,11 @@ def prediction_loop(model, dataloader: Iterable[Dict[str, object]], compute_metr
     the reference does.  ``compact_spots=True`` compacts the five score maps of each batch right after its forward, and the
     five label maps the same way (sparse labels through ``ops.spots_to_tags`` first, which keeps "last spot wins"), drops the
     tensors and hands ``compute_metrics`` spot lists ``[(i, j, tag, score)]`` in their place; ``decode_peneo`` /
-    ``sample_decode_peneo`` take either, and the metrics are the same."""
+    ``sample_decode_peneo`` take either, and the metrics are the same.
+
+    A model with ``set_skip_padded_pairs(True)`` needs no argument here: its maps hold the background row at every pair that
+    touches the padding, so predicted spots in the padding disappear (with either ``compact_spots`` setting), and the reported
+    eval losses are the live-pair losses of ``PEneoOutput``, not the reference's means over all pairs."""
     if device is None:
         device = next(model.parameters()).device
     compute_metrics = compute_metrics or make_compute_metrics()
