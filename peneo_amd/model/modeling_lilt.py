@@ -6,18 +6,22 @@ shared attention scores (BiACM, :398-404).  Parameter names reproduce the refere
 ``attention.output`` / ``attention.layout_output``, ``intermediate`` / ``layout_intermediate``,
 ``output`` / ``layout_output``).
 
-Device mapping: per layer two fused QKV GEMMs (text, layout); q/k/v of both streams are concatenated per head
-(``peneo_head_concat``, q pre-scaled by 1/sqrt(d) resp. 1/sqrt(d_l)) so ONE flash-attention call over head dim
-d + d_l produces the summed scores, one softmax and both context streams; the rest is the same
-GEMM(+bias/GELU/residual/dropout) + LayerNorm chain as LayoutLMv3, once per stream.  Deviation in *train* mode
-only: the reference draws two independent attention-dropout masks for the two (identical) probability
-matrices; here both streams share one mask.
+Device mapping: per layer two fused QKV GEMMs (text, layout), the attention, then the same GEMM(+bias/GELU/residual/dropout) +
+LayerNorm chain as LayoutLMv3 for the two streams in lock step.  ``lilt_route`` decides once per forward how a step runs
+(``LiltRoute``); every layer's forward and backward follow it.  The attention is one of three arms.  "concat": q/k/v of both
+streams are concatenated per head (``peneo_head_concat``, q pre-scaled by 1/sqrt(d) resp. 1/sqrt(d_l)) so ONE flash-attention
+call over head dim d + d_l produces the summed scores, one softmax and both context streams.  "attn2_eval" (forwards without
+autograd and attention dropout) and "attn2_train" (opt-in) run the two-stream kernels on the QKV buffers as they are, bit-identical
+to it and without the packed copies.  On the grouped route every pair of same-role GEMMs of the two streams is one
+``ops.gemm_group`` launch.  Deviation in *train* mode only: the reference draws two independent attention-dropout masks for the
+two (identical) probability matrices; here both streams share one mask.
 """
 from __future__ import annotations
 
 import math
 import os
-from typing import List
+from dataclasses import dataclass
+from typing import List, NamedTuple
 
 import torch
 import torch.nn as nn
@@ -99,53 +103,105 @@ class LiltLayoutEmbeddings(nn.Module):
 
 
 # ------------------------------------------------------------------------------------------------
-# shared per-stream pieces: everything of a transformer layer after the attention context
+# everything of a transformer layer after the attention context, the two streams in lock step: every pair of same-role Linear
+# layers is ONE grouped launch on the grouped route (ops.gemm_group with per-problem epilogues).  The layout stream's GEMMs
+# ([4096, 192] x [192, 576] ...) are all fixed cost on their own (11-18 us for 1-2 us of MFMA work), and a LiLT step issued launch
+# by launch is host-bound (18.5 ms of host against 20 ms of device time).
 # ------------------------------------------------------------------------------------------------
-def _post_attn_fwd(wc: WeightCache, key: str, dt, eps, seeds: DropoutSeeds, site: int, x, att, params):
-    wo, bo, g1, b1, wi, bi, wo2, bo2, g2, b2 = params
-    Wo, Wi, Wo2 = wc.cast(key + ".o", wo, dt), wc.cast(key + ".i", wi, dt), wc.cast(key + ".o2", wo2, dt)
-    h1 = ops.gemm(att, Wo, bias=bo, residual=x, drop_p=seeds.p_hidden, drop_seed=seeds.seed(site))
-    a, m1, r1 = ops.layernorm_fwd(h1, g1, b1, eps)
-    zi = torch.empty((x.shape[0], wi.shape[0]), dtype=dt, device=x.device)
-    inter = ops.gemm(a, Wi, bias=bi, act=ACT_GELU, preact=zi)
-    h2 = ops.gemm(inter, Wo2, bias=bo2, residual=a, drop_p=seeds.p_hidden, drop_seed=seeds.seed(site + 1))
-    out, m2, r2 = ops.layernorm_fwd(h2, g2, b2, eps)
-    return out, (att, h1, m1, r1, a, zi, inter, h2, m2, r2)
+def _gemms(grouped: bool, problems, **layout) -> List[torch.Tensor]:
+    """Same-role products of the two streams, [(A, B, epilogue options), ...]: one ops.gemm_group launch on the grouped route,
+    else one ops.gemm each, in order."""
+    if grouped:
+        return ops.gemm_group([(a, b, None, ep) for a, b, ep in problems], **layout)
+    return [ops.gemm(a, b, **layout, **ep) for a, b, ep in problems]
 
 
-def _post_attn_bwd(wc: WeightCache, key: str, dt, seeds: DropoutSeeds, site: int, d_out, saved, params, on_side):
-    """-> (d_att, d_x_residual, grads in parameter order).  ``on_side(fn, operands)`` runs the parameter-gradient work
-    (wgrad GEMMs, bias column sums) on the stage's second stream, off the activation-gradient critical path; ``operands``
-    are the tensors that work READS (kept alive until the join).  Its outputs are never kept: they are returned as
-    gradients, and an extra reference would make AccumulateGrad clone them on the main stream instead of storing them."""
-    wo, bo, g1, b1, wi, bi, wo2, bo2, g2, b2 = params
-    att, h1, m1, r1, a, zi, inter, h2, m2, r2 = saved
-    Wo, Wi, Wo2 = wc.cast(key + ".o", wo, dt), wc.cast(key + ".i", wi, dt), wc.cast(key + ".o2", wo2, dt)
-    dev = d_out.device
-    Hs, Is = wo.shape[0], wi.shape[0]
-    wgrad = lambda dy, xin: ops.gemm(dy, xin, a_kmajor=False, b_kmajor=False, out_dtype=torch.float32)
-    pool = torch.zeros(4 * Hs + (Hs + Is + Hs), dtype=torch.float32, device=dev)   # one fill for all small accumulators
-    dg2, db2, dg1, db1 = pool[:Hs], pool[Hs:2 * Hs], pool[2 * Hs:3 * Hs], pool[3 * Hs:4 * Hs]
-    dbo2, dbi, dbo = pool[4 * Hs:5 * Hs], pool[5 * Hs:5 * Hs + Is], pool[5 * Hs + Is:]
-    d_dense2 = torch.empty_like(h2) if seeds.p_hidden > 0 else None
-    d_h2 = ops.layernorm_bwd(d_out.contiguous(), h2, g2, m2, r2, dg2, db2, dx_dropped=d_dense2, drop2_p=seeds.p_hidden,
-                             drop2_seed=seeds.seed(site + 1))
-    if d_dense2 is None:
-        d_dense2 = d_h2
-    _, dwo2 = on_side(lambda: (ops.colsum(d_dense2, out=dbo2, accumulate=True), wgrad(d_dense2, inter)),
-                      (d_dense2, inter))
-    d_zi = ops.gemm(d_dense2, Wo2, b_kmajor=False, grad_src=zi, grad_act=ACT_GELU)
-    _, dwi = on_side(lambda: (ops.colsum(d_zi, out=dbi, accumulate=True), wgrad(d_zi, a)), (d_zi, a))
-    d_a = ops.gemm(d_zi, Wi, b_kmajor=False, residual=d_h2)
-    d_dense1 = torch.empty_like(h1) if seeds.p_hidden > 0 else None
-    d_h1 = ops.layernorm_bwd(d_a, h1, g1, m1, r1, dg1, db1, dx_dropped=d_dense1, drop2_p=seeds.p_hidden,
-                             drop2_seed=seeds.seed(site))
-    if d_dense1 is None:
-        d_dense1 = d_h1
-    _, dwo = on_side(lambda: (ops.colsum(d_dense1, out=dbo, accumulate=True), wgrad(d_dense1, att)),
-                     (d_dense1, att))
-    d_att = ops.gemm(d_dense1, Wo, b_kmajor=False)
-    return d_att, d_h1, (dwo, dbo, dg1, db1, dwi, dbi, dwo2, dbo2, dg2, db2)
+class _PostParams(NamedTuple):
+    """one stream's parameters behind the attention, in parameter order (_post_params)"""
+    wo: torch.Tensor
+    bo: torch.Tensor
+    g1: torch.Tensor
+    b1: torch.Tensor
+    wi: torch.Tensor
+    bi: torch.Tensor
+    wo2: torch.Tensor
+    bo2: torch.Tensor
+    g2: torch.Tensor
+    b2: torch.Tensor
+
+    def cast(self, wc: WeightCache, key: str, dt):
+        return wc.cast(key + ".o", self.wo, dt), wc.cast(key + ".i", self.wi, dt), wc.cast(key + ".o2", self.wo2, dt)
+
+
+def _post_attn_fwd(wc: WeightCache, idx: int, dt, eps, seeds: DropoutSeeds, grouped: bool, site_t, site_l, x, att, tp, l, latt, lp):
+    """out-proj + residual -> LN -> FFN1 + GELU -> FFN2 + residual -> LN.  -> (out, lout, saved text, saved layout)"""
+    Wo, Wi, Wo2 = tp.cast(wc, f"L{idx}.t", dt)
+    lWo, lWi, lWo2 = lp.cast(wc, f"L{idx}.l", dt)
+    p = seeds.p_hidden
+    h1, lh1 = _gemms(grouped, [(att, Wo, dict(bias=tp.bo, residual=x, drop_p=p, drop_seed=seeds.seed(site_t))),
+                               (latt, lWo, dict(bias=lp.bo, residual=l, drop_p=p, drop_seed=seeds.seed(site_l)))])
+    a, m1, r1 = ops.layernorm_fwd(h1, tp.g1, tp.b1, eps)
+    la, lm1, lr1 = ops.layernorm_fwd(lh1, lp.g1, lp.b1, eps)
+    zi = torch.empty((x.shape[0], tp.wi.shape[0]), dtype=dt, device=x.device)
+    lzi = torch.empty((l.shape[0], lp.wi.shape[0]), dtype=dt, device=x.device)
+    inter, linter = _gemms(grouped, [(a, Wi, dict(bias=tp.bi, act=ACT_GELU, preact=zi)),
+                                     (la, lWi, dict(bias=lp.bi, act=ACT_GELU, preact=lzi))])
+    h2, lh2 = _gemms(grouped, [(inter, Wo2, dict(bias=tp.bo2, residual=a, drop_p=p, drop_seed=seeds.seed(site_t + 1))),
+                               (linter, lWo2, dict(bias=lp.bo2, residual=la, drop_p=p, drop_seed=seeds.seed(site_l + 1)))])
+    out, m2, r2 = ops.layernorm_fwd(h2, tp.g2, tp.b2, eps)
+    lout, lm2, lr2 = ops.layernorm_fwd(lh2, lp.g2, lp.b2, eps)
+    return out, lout, (att, h1, m1, r1, a, zi, inter, h2, m2, r2), (latt, lh1, lm1, lr1, la, lzi, linter, lh2, lm2, lr2)
+
+
+def _post_attn_bwd(wc: WeightCache, idx: int, dt, seeds: DropoutSeeds, grouped: bool, site_t, site_l, d_out, d_lout, sv_t, sv_l,
+                   tp, lp, on_side):
+    """-> (d_att, d_x_residual, text grads, d_latt, d_l_residual, layout grads, wg_t, wg_l): the three dgrad GEMM pairs on the main
+    stream; ``on_side(fn, operands)`` runs the bias column sums on the stage's second stream, off the activation-gradient critical
+    path (``operands``: the tensors that work READS, kept alive until the join; its outputs are never kept: they are returned as
+    gradients, and an extra reference would make AccumulateGrad clone them on the main stream instead of storing them).  The six
+    weight gradients leave as operand pairs (wg_t -> dwi, dwo2, dwo; wg_l likewise; their slots in the grads are None): the caller
+    runs them behind the attention backward, together with the two QKV weight gradients - on the grouped route as TWO grouped
+    launches (four text, four layout; each tile with its full K = tokens) instead of split-k launches + reductions, the schedule
+    that measured best for the LayoutLMv3 layer (csrc/stages.hip), and 7 launches per layer less for a step that is close to
+    host-bound."""
+    att, h1, m1, r1, a, zi, inter, h2, m2, r2 = sv_t
+    latt, lh1, lm1, lr1, la, lzi, linter, lh2, lm2, lr2 = sv_l
+    Wo, Wi, Wo2 = tp.cast(wc, f"L{idx}.t", dt)
+    lWo, lWi, lWo2 = lp.cast(wc, f"L{idx}.l", dt)
+    Hs, Is, Hl, Il = tp.wo.shape[0], tp.wi.shape[0], lp.wo.shape[0], lp.wi.shape[0]
+    sizes = [Hs] * 5 + [Is, Hs] + [Hl] * 5 + [Il, Hl]
+    pool = torch.zeros(sum(sizes), dtype=torch.float32, device=d_out.device)   # one fill for all small accumulators
+    dg2, db2, dg1, db1, dbo2, dbi, dbo, ldg2, ldb2, ldg1, ldb1, ldbo2, ldbi, ldbo = pool.split(sizes)
+    p = seeds.p_hidden
+
+    def ln_bwd(site, dy, h, g, m, r, dg, db):
+        """-> (d_h, the same behind the dropout of the Linear in front: LayerNorm's dx_dropped output, d_h itself without dropout)"""
+        dd = torch.empty_like(h) if p > 0 else None
+        d_h = ops.layernorm_bwd(dy, h, g, m, r, dg, db, dx_dropped=dd, drop2_p=p, drop2_seed=seeds.seed(site))
+        return d_h, (dd if p > 0 else d_h)
+
+    d_h2, d_dense2 = ln_bwd(site_t + 1, d_out.contiguous(), h2, tp.g2, m2, r2, dg2, db2)
+    d_lh2, d_ldense2 = ln_bwd(site_l + 1, d_lout.contiguous(), lh2, lp.g2, lm2, lr2, ldg2, ldb2)
+    d_zi, d_lzi = _gemms(grouped, [(d_dense2, Wo2, dict(grad_src=zi, grad_act=ACT_GELU)),
+                                   (d_ldense2, lWo2, dict(grad_src=lzi, grad_act=ACT_GELU))], b_kmajor=False)
+    d_a, d_la = _gemms(grouped, [(d_zi, Wi, dict(residual=d_h2)), (d_lzi, lWi, dict(residual=d_lh2))], b_kmajor=False)
+    d_h1, d_dense1 = ln_bwd(site_t, d_a, h1, tp.g1, m1, r1, dg1, db1)
+    d_lh1, d_ldense1 = ln_bwd(site_l, d_la, lh1, lp.g1, lm1, lr1, ldg1, ldb1)
+    d_att, d_latt = _gemms(grouped, [(d_dense1, Wo, {}), (d_ldense1, lWo, {})], b_kmajor=False)
+
+    def side_work():
+        ops.colsum(d_dense2, out=dbo2, accumulate=True)
+        ops.colsum(d_zi, out=dbi, accumulate=True)
+        ops.colsum(d_dense1, out=dbo, accumulate=True)
+        ops.colsum(d_ldense2, out=ldbo2, accumulate=True)
+        ops.colsum(d_lzi, out=ldbi, accumulate=True)
+        ops.colsum(d_ldense1, out=ldbo, accumulate=True)
+    on_side(side_work, (d_dense2, d_zi, d_dense1, d_ldense2, d_lzi, d_ldense1))
+    wg_t = [(d_zi, a), (d_dense2, inter), (d_dense1, att)]                 # -> dwi, dwo2, dwo
+    wg_l = [(d_lzi, la), (d_ldense2, linter), (d_ldense1, latt)]          # -> ldwi, ldwo2, ldwo
+    gt = (None, dbo, dg1, db1, None, dbi, None, dbo2, dg2, db2)
+    gl = (None, ldbo, ldg1, ldb1, None, ldbi, None, ldbo2, ldg2, ldb2)
+    return d_att, d_h1, gt, d_latt, d_lh1, gl, wg_t, wg_l
 
 
 class _State:
@@ -154,8 +210,33 @@ class _State:
         self.seeds = None
         self.dtype = torch.float32
         self.dims = None
-        self.attn2 = False        # this forward's attention runs as the two-stream kernel (_use_attn2)
-        self.attn2_train = False  # ... as the two-stream forward with dropout + the two-stream backward (_use_attn2_train)
+        self.route = None         # this forward's LiltRoute
+
+
+@dataclass(frozen=True)
+class LiltRoute:
+    """Which launches one step of the layer stages runs.  ``lilt_route`` decides it once per forward (LiltModel.forward); every layer's
+    forward and backward dispatch on the route the forward stored and read no switch again, so a switch changed between the forward
+    and the backward of one step does not affect that step."""
+    attention: str      # "attn2_eval": ops.attn2_fwd, nothing kept | "attn2_train": attn2_fwd with the keep words + attn2_bwd | "concat"
+    grouped: bool       # the layers issue their same-role GEMM pairs as ops.gemm_group
+    defer_join: bool    # the layers defer the side-stream join by one stage (where engine.can_defer allows it at backward time)
+
+
+def lilt_route(cfg: LiltConfig, dt: torch.dtype, seeds: DropoutSeeds, grad_enabled: bool) -> LiltRoute:
+    """The route of a forward at compute dtype `dt` from the widths, the switches and the library's host-side query (no GPU).
+    grad_enabled: torch.is_grad_enabled() of the caller (it is always off inside an autograd.Function).  The two-stream attention is
+    bit-identical to the concat path it replaces (tests/test_gpu_attn2.py, tests/test_gpu_attn2_bwd.py); forwards without autograd
+    and without attention dropout take it unless PENEO_LILT_ATTN2=0, training forwards only with PENEO_LILT_ATTN2_TRAIN=1."""
+    H, nh, r, I = cfg.hidden_size, cfg.num_attention_heads, cfg.channel_shrink_ratio, cfg.intermediate_size
+    env, bf16 = os.environ.get, dt == torch.bfloat16
+    train = grad_enabled or seeds.p_attn > 0.0
+    switch = env("PENEO_LILT_ATTN2_TRAIN", "0") == "1" if train else env("PENEO_LILT_ATTN2", "1") != "0"
+    attention = "concat"
+    if bf16 and switch and ops.attn2_supported(dt, H // nh, H // r // nh):
+        attention = "attn2_train" if train else "attn2_eval"
+    grouped = bf16 and all(w % 8 == 0 for w in (H, H // r, I, I // r)) and env("PENEO_LILT_GROUPS", "1") != "0"
+    return LiltRoute(attention, grouped, env("PENEO_DEFER_JOIN", "1") != "0")
 
 
 class _LiltEmbedStage(torch.autograd.Function):
@@ -230,204 +311,122 @@ class _LiltEmbedStage(torch.autograd.Function):
 
 
 # ------------------------------------------------------------------------------------------------
-# bf16: the two streams in lock step, every pair of same-role Linear layers as ONE grouped launch (ops.gemm_group with
-# per-problem epilogues).  The layout stream's GEMMs ([4096, 192] x [192, 576] ...) are all fixed cost on their own (11-18 us
-# for 1-2 us of MFMA work), and a LiLT step issued launch by launch is host-bound (18.5 ms of host against 20 ms of device time).
+# the attention of a layer, one arm per LiltRoute.attention.  Forward: (cfg, st, idx, qkv, lqkv) -> (att, latt, kept); backward:
+# (cfg, st, idx, kept, att, latt, d_att, d_latt, dqkv, dlqkv) fills dqkv / dlqkv.  `kept` is the arm's own: only its backward reads it.
 # ------------------------------------------------------------------------------------------------
-def _use_groups(dt, *dims) -> bool:
-    return dt == torch.bfloat16 and all(d % 8 == 0 for d in dims) and os.environ.get("PENEO_LILT_GROUPS", "1") != "0"
+def _geometry(cfg, st):
+    H, nh = cfg.hidden_size, cfg.num_attention_heads
+    Hl = H // cfg.channel_shrink_ratio
+    return st.dims[0], st.dims[1], H, Hl, nh, H // nh, Hl // nh
 
 
-def _post_attn_fwd2(wc, idx, dt, eps, seeds, site_t, site_l, x, att, tp, l, latt, lp):
-    (wo, bo, g1, b1, wi, bi, wo2, bo2, g2, b2), (lwo, lbo, lg1, lb1, lwi, lbi, lwo2, lbo2, lg2, lb2) = tp, lp
-    kt, kl = f"L{idx}.t", f"L{idx}.l"
-    Wo, Wi, Wo2 = wc.cast(kt + ".o", wo, dt), wc.cast(kt + ".i", wi, dt), wc.cast(kt + ".o2", wo2, dt)
-    lWo, lWi, lWo2 = wc.cast(kl + ".o", lwo, dt), wc.cast(kl + ".i", lwi, dt), wc.cast(kl + ".o2", lwo2, dt)
-    h1, lh1 = ops.gemm_group([(att, Wo, None, dict(bias=bo, residual=x, drop_p=seeds.p_hidden, drop_seed=seeds.seed(site_t))),
-                              (latt, lWo, None, dict(bias=lbo, residual=l, drop_p=seeds.p_hidden, drop_seed=seeds.seed(site_l)))])
-    a, m1, r1 = ops.layernorm_fwd(h1, g1, b1, eps)
-    la, lm1, lr1 = ops.layernorm_fwd(lh1, lg1, lb1, eps)
-    zi = torch.empty((x.shape[0], wi.shape[0]), dtype=dt, device=x.device)
-    lzi = torch.empty((l.shape[0], lwi.shape[0]), dtype=dt, device=x.device)
-    inter, linter = ops.gemm_group([(a, Wi, None, dict(bias=bi, act=ACT_GELU, preact=zi)),
-                                    (la, lWi, None, dict(bias=lbi, act=ACT_GELU, preact=lzi))])
-    h2, lh2 = ops.gemm_group([(inter, Wo2, None, dict(bias=bo2, residual=a, drop_p=seeds.p_hidden, drop_seed=seeds.seed(site_t + 1))),
-                              (linter, lWo2, None, dict(bias=lbo2, residual=la, drop_p=seeds.p_hidden, drop_seed=seeds.seed(site_l + 1)))])
-    out, m2, r2 = ops.layernorm_fwd(h2, g2, b2, eps)
-    lout, lm2, lr2 = ops.layernorm_fwd(lh2, lg2, lb2, eps)
-    return out, lout, (att, h1, m1, r1, a, zi, inter, h2, m2, r2), (latt, lh1, lm1, lr1, la, lzi, linter, lh2, lm2, lr2)
+def _thirds(t):
+    w = t.shape[1] // 3
+    return t[:, :w], t[:, w:2 * w], t[:, 2 * w:]
 
 
-def _post_attn_bwd2(wc, idx, dt, seeds, site_t, site_l, d_out, d_lout, sv_t, sv_l, tp, lp, on_side):
-    """Both streams' post-attention backward in lock step: the three dgrad GEMM pairs as grouped launches on the main stream, the
-    text weight gradients one by one (split-k) and the FOUR layout weight gradients of this half as one grouped launch (each tile
-    with its full K = tokens: 38 long workgroups instead of four split-k launches + four reductions) on the side stream."""
-    (wo, bo, g1, b1, wi, bi, wo2, bo2, g2, b2), (lwo, lbo, lg1, lb1, lwi, lbi, lwo2, lbo2, lg2, lb2) = tp, lp
-    att, h1, m1, r1, a, zi, inter, h2, m2, r2 = sv_t
-    latt, lh1, lm1, lr1, la, lzi, linter, lh2, lm2, lr2 = sv_l
-    kt, kl = f"L{idx}.t", f"L{idx}.l"
-    Wo, Wi, Wo2 = wc.cast(kt + ".o", wo, dt), wc.cast(kt + ".i", wi, dt), wc.cast(kt + ".o2", wo2, dt)
-    lWo, lWi, lWo2 = wc.cast(kl + ".o", lwo, dt), wc.cast(kl + ".i", lwi, dt), wc.cast(kl + ".o2", lwo2, dt)
-    dev = d_out.device
-    Hs, Is, Hl, Il = wo.shape[0], wi.shape[0], lwo.shape[0], lwi.shape[0]
-    wgrad = lambda dy, xin: ops.gemm(dy, xin, a_kmajor=False, b_kmajor=False, out_dtype=torch.float32)
-    pool = torch.zeros(4 * Hs + (Hs + Is + Hs) + 4 * Hl + (Hl + Il + Hl), dtype=torch.float32, device=dev)   # one fill for all small accumulators
-    dg2, db2, dg1, db1 = pool[:Hs], pool[Hs:2 * Hs], pool[2 * Hs:3 * Hs], pool[3 * Hs:4 * Hs]
-    o = 4 * Hs
-    dbo2, dbi, dbo = pool[o:o + Hs], pool[o + Hs:o + Hs + Is], pool[o + Hs + Is:o + 2 * Hs + Is]
-    o += 2 * Hs + Is
-    ldg2, ldb2, ldg1, ldb1 = pool[o:o + Hl], pool[o + Hl:o + 2 * Hl], pool[o + 2 * Hl:o + 3 * Hl], pool[o + 3 * Hl:o + 4 * Hl]
-    o += 4 * Hl
-    ldbo2, ldbi, ldbo = pool[o:o + Hl], pool[o + Hl:o + Hl + Il], pool[o + Hl + Il:]
-    drop = seeds.p_hidden > 0
-    d_dense2 = torch.empty_like(h2) if drop else None
-    d_ldense2 = torch.empty_like(lh2) if drop else None
-    d_h2 = ops.layernorm_bwd(d_out.contiguous(), h2, g2, m2, r2, dg2, db2, dx_dropped=d_dense2, drop2_p=seeds.p_hidden,
-                             drop2_seed=seeds.seed(site_t + 1))
-    d_lh2 = ops.layernorm_bwd(d_lout.contiguous(), lh2, lg2, lm2, lr2, ldg2, ldb2, dx_dropped=d_ldense2, drop2_p=seeds.p_hidden,
-                              drop2_seed=seeds.seed(site_l + 1))
-    if not drop:
-        d_dense2, d_ldense2 = d_h2, d_lh2
-    d_zi, d_lzi = ops.gemm_group([(d_dense2, Wo2, None, dict(grad_src=zi, grad_act=ACT_GELU)),
-                                  (d_ldense2, lWo2, None, dict(grad_src=lzi, grad_act=ACT_GELU))], b_kmajor=False)
-    d_a, d_la = ops.gemm_group([(d_zi, Wi, None, dict(residual=d_h2)), (d_lzi, lWi, None, dict(residual=d_lh2))], b_kmajor=False)
-    d_dense1 = torch.empty_like(h1) if drop else None
-    d_ldense1 = torch.empty_like(lh1) if drop else None
-    d_h1 = ops.layernorm_bwd(d_a, h1, g1, m1, r1, dg1, db1, dx_dropped=d_dense1, drop2_p=seeds.p_hidden, drop2_seed=seeds.seed(site_t))
-    d_lh1 = ops.layernorm_bwd(d_la, lh1, lg1, lm1, lr1, ldg1, ldb1, dx_dropped=d_ldense1, drop2_p=seeds.p_hidden,
-                              drop2_seed=seeds.seed(site_l))
-    if not drop:
-        d_dense1, d_ldense1 = d_h1, d_lh1
-    d_att, d_latt = ops.gemm_group([(d_dense1, Wo, None), (d_ldense1, lWo, None)], b_kmajor=False)
-
-    # Round 5: only the bias column sums start here.  The six weight gradients of this half leave as operand pairs: the caller
-    # runs them behind the attention backward, together with the two QKV weight gradients, as TWO grouped launches (four text,
-    # four layout; each tile with its full K) instead of four split-k launches + reductions and two groups - the schedule that
-    # measured best for the LayoutLMv3 layer (csrc/stages.hip), and 7 launches per layer less for a step that is close to host-bound
-    def side_work():
-        ops.colsum(d_dense2, out=dbo2, accumulate=True)
-        ops.colsum(d_zi, out=dbi, accumulate=True)
-        ops.colsum(d_dense1, out=dbo, accumulate=True)
-        ops.colsum(d_ldense2, out=ldbo2, accumulate=True)
-        ops.colsum(d_lzi, out=ldbi, accumulate=True)
-        ops.colsum(d_ldense1, out=ldbo, accumulate=True)
-    on_side(side_work, (d_dense2, d_zi, d_dense1, d_ldense2, d_lzi, d_ldense1))
-    wg_t = [(d_zi, a), (d_dense2, inter), (d_dense1, att)]                 # -> dwi, dwo2, dwo
-    wg_l = [(d_lzi, la), (d_ldense2, linter), (d_ldense1, latt)]          # -> ldwi, ldwo2, ldwo
-    gt = (None, dbo, dg1, db1, None, dbi, None, dbo2, dg2, db2)
-    gl = (None, ldbo, ldg1, ldb1, None, ldbi, None, ldbo2, ldg2, ldb2)
-    return d_att, d_h1, gt, d_latt, d_lh1, gl, wg_t, wg_l
+def _contexts(qkv, lqkv):
+    return qkv.new_empty((qkv.shape[0], qkv.shape[1] // 3)), lqkv.new_empty((lqkv.shape[0], lqkv.shape[1] // 3))
 
 
-def _use_attn2(dt, seeds, d, dl) -> bool:
-    """The two-stream attention forward (ops.attn2_fwd) instead of head_concat x 2 + attn_fwd + head_split: forwards without
-    autograd and without attention dropout, where the kernel takes the widths.  It is bit-identical to the path it replaces
-    (tests/test_gpu_attn2.py); PENEO_LILT_ATTN2=0, read at call time, keeps the concat path."""
-    return (dt == torch.bfloat16 and not torch.is_grad_enabled() and seeds.p_attn <= 0.0 and ops.attn2_supported(dt, d, dl)
-            and os.environ.get("PENEO_LILT_ATTN2", "1") != "0")
+def _attn2_eval_fwd(cfg, st, idx, qkv, lqkv):
+    """no autograd, no attention dropout: the two-stream kernel reads q | k | v where the QKV GEMMs left them and writes both context
+    streams - no packed copy `cat`, no `attc`, nothing kept for a backward"""
+    B, S, _, _, nh, d, dl = _geometry(cfg, st)
+    att, latt = _contexts(qkv, lqkv)
+    ops.attn2_fwd(*_thirds(qkv), *_thirds(lqkv), B, nh, S, 1.0 / math.sqrt(d), 1.0 / math.sqrt(dl), st.key_bias, out_a=att, out_b=latt)
+    return att, latt, ()
 
 
-def _use_attn2_train(dt, seeds, d, dl) -> bool:
-    """The two-stream attention for TRAINING forwards (autograd enabled or attention dropout active): ops.attn2_fwd with the
-    layer's keep words and ops.attn2_bwd instead of the concat path - no `cat`, no `attc`, no packed gradient copies.  Opt-in:
-    PENEO_LILT_ATTN2_TRAIN=1, read at call time; off by default.  Bit-identical to the path it replaces (tests/test_gpu_attn2_bwd.py)."""
-    return (dt == torch.bfloat16 and (torch.is_grad_enabled() or seeds.p_attn > 0.0) and ops.attn2_supported(dt, d, dl)
-            and os.environ.get("PENEO_LILT_ATTN2_TRAIN", "0") == "1")
+def _attn2_train_fwd(cfg, st, idx, qkv, lqkv):
+    """the training form of the above: the same kernel with the layer's keep words; the backward reads qkv / lqkv in place"""
+    B, S, _, _, nh, d, dl = _geometry(cfg, st)
+    att, latt = _contexts(qkv, lqkv)
+    _, _, lse = ops.attn2_fwd(*_thirds(qkv), *_thirds(lqkv), B, nh, S, 1.0 / math.sqrt(d), 1.0 / math.sqrt(dl), st.key_bias,
+                              out_a=att, out_b=latt, drop_p=st.seeds.p_attn,
+                              drop_words=st.seeds.attn_words(idx, cfg.num_hidden_layers, B, nh, S, qkv.device))
+    return att, latt, (qkv, lqkv, lse)
+
+
+def _attn2_train_bwd(cfg, st, idx, kept, att, latt, d_att, d_latt, dqkv, dlqkv):
+    B, S, _, _, nh, d, dl = _geometry(cfg, st)
+    qkv, lqkv, lse = kept
+    ops.attn2_bwd(*_thirds(qkv), *_thirds(lqkv), att, d_att, latt, d_latt, lse, B, nh, S, 1.0 / math.sqrt(d), 1.0 / math.sqrt(dl),
+                  st.key_bias, dqkv, dlqkv, drop_p=st.seeds.p_attn,
+                  drop_words=st.seeds.attn_words(idx, cfg.num_hidden_layers, B, nh, S, dqkv.device))
+
+
+def _concat_fwd(cfg, st, idx, qkv, lqkv):
+    """q/k/v of both streams packed per head (q pre-scaled), ONE attention call at head dim d + d_l, the context unpacked"""
+    B, S, H, Hl, nh, d, dl = _geometry(cfg, st)
+    w = nh * (d + dl)
+    cat = torch.empty((qkv.shape[0], 3 * w), dtype=qkv.dtype, device=qkv.device)
+    ops.head_concat(qkv[:, :H], lqkv[:, :Hl], nh, cat[:, :w], 1.0 / math.sqrt(d), 1.0 / math.sqrt(dl))
+    ops.head_concat(qkv[:, H:], lqkv[:, Hl:], 2 * nh, cat[:, w:])      # k and v in one launch: 2 nh "heads"
+    attc, lse = ops.attn_fwd(*_thirds(cat), B, nh, S, d + dl, 1.0, None, st.key_bias, drop_p=st.seeds.p_attn,
+                             drop_words=st.seeds.attn_words(idx, cfg.num_hidden_layers, B, nh, S, qkv.device))
+    att, latt = _contexts(qkv, lqkv)
+    ops.head_split(attc, nh, att, latt)
+    return att, latt, (cat, attc, lse)
+
+
+def _concat_bwd(cfg, st, idx, kept, att, latt, d_att, d_latt, dqkv, dlqkv):
+    B, S, H, Hl, nh, d, dl = _geometry(cfg, st)
+    w = nh * (d + dl)
+    cat, attc, lse = kept
+    d_attc = torch.empty((cat.shape[0], w), dtype=cat.dtype, device=cat.device)
+    ops.head_concat(d_att, d_latt, nh, d_attc)
+    dcat = torch.empty_like(cat)
+    ops.attn_bwd(*_thirds(cat), attc, d_attc, lse, B, nh, S, d + dl, 1.0, None, st.key_bias, dcat, None, drop_p=st.seeds.p_attn,
+                 drop_words=st.seeds.attn_words(idx, cfg.num_hidden_layers, B, nh, S, dcat.device))
+    ops.head_split(dcat[:, :w], nh, dqkv[:, :H], dlqkv[:, :Hl], 1.0 / math.sqrt(d), 1.0 / math.sqrt(dl))
+    ops.head_split(dcat[:, w:], 2 * nh, dqkv[:, H:], dlqkv[:, Hl:])
+
+
+_ATTN_FWD = {"attn2_eval": _attn2_eval_fwd, "attn2_train": _attn2_train_fwd, "concat": _concat_fwd}
+_ATTN_BWD = {"attn2_train": _attn2_train_bwd, "concat": _concat_bwd}
+
+
+class _LayerSaved(NamedTuple):
+    """what a layer's forward leaves for its backward"""
+    x: torch.Tensor
+    l: torch.Tensor
+    attn: tuple       # the attention arm's kept tensors; ctx.route.attention says whose (_ATTN_BWD reads them)
+    post_t: tuple     # _post_attn_fwd's saved activations, text stream (att first)
+    post_l: tuple     # ... layout stream (latt first)
 
 
 class _LiltLayerStage(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, st, idx, x, l, *params):
         (wq, bq, wk, bk, wv, bv, lwq, lbq, lwk, lbk, lwv, lbv, *rest) = params
-        tp, lp = rest[:10], rest[10:]
-        cfg, wc, dt = model.config, model.weight_cache, st.dtype
-        B, S = st.dims
-        H, nh = cfg.hidden_size, cfg.num_attention_heads
-        Hl = H // cfg.channel_shrink_ratio
-        d, dl = H // nh, Hl // nh
-        dc = d + dl
-        seeds = st.seeds
+        tp, lp = _PostParams(*rest[:10]), _PostParams(*rest[10:])
+        cfg, wc, dt, route = model.config, model.weight_cache, st.dtype, st.route
         site = 32 * (idx + 1)
-        dev = x.device
         Wqkv = wc.cat_rows(f"L{idx}.qkv", [wq, wk, wv], dt)
         bqkv = wc.cat_vec(f"L{idx}.bqkv", [bq, bk, bv], [bq.numel(), bk.numel(), bv.numel()])
         Wlqkv = wc.cat_rows(f"L{idx}.lqkv", [lwq, lwk, lwv], dt)
         blqkv = wc.cat_vec(f"L{idx}.blqkv", [lbq, lbk, lbv], [lbq.numel(), lbk.numel(), lbv.numel()])
-        grouped = _use_groups(dt, H, Hl, tp[4].shape[0], lp[4].shape[0])
-        if grouped:
-            qkv, lqkv = ops.gemm_group([(x, Wqkv, None, dict(bias=bqkv)), (l, Wlqkv, None, dict(bias=blqkv))])
-        else:
-            qkv = ops.gemm(x, Wqkv, bias=bqkv)          # [R, 3H]
-            lqkv = ops.gemm(l, Wlqkv, bias=blqkv)       # [R, 3Hl]
-        R = x.shape[0]
-        if st.attn2:
-            # no autograd, no attention dropout (LiltModel.forward decided): the two-stream kernel reads q | k | v where the QKV GEMMs
-            # left them and writes both context streams - no packed copy `cat`, no `attc`, nothing saved for a backward
-            att = torch.empty((R, H), dtype=dt, device=dev)
-            latt = torch.empty((R, Hl), dtype=dt, device=dev)
-            ops.attn2_fwd(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], lqkv[:, :Hl], lqkv[:, Hl:2 * Hl], lqkv[:, 2 * Hl:], B, nh, S,
-                          1.0 / math.sqrt(d), 1.0 / math.sqrt(dl), st.key_bias, out_a=att, out_b=latt)
-            if grouped:
-                xo, lo, _, _ = _post_attn_fwd2(wc, idx, dt, cfg.layer_norm_eps, seeds, site + 2, site + 6, x, att, tp, l, latt, lp)
-            else:
-                xo, _ = _post_attn_fwd(wc, f"L{idx}.t", dt, cfg.layer_norm_eps, seeds, site + 2, x, att, tp)
-                lo, _ = _post_attn_fwd(wc, f"L{idx}.l", dt, cfg.layer_norm_eps, seeds, site + 6, l, latt, lp)
-            return xo, lo
-        if st.attn2_train:
-            # the training form of the above: the same kernel with the layer's keep words; the backward reads qkv / lqkv in place
-            att = torch.empty((R, H), dtype=dt, device=dev)
-            latt = torch.empty((R, Hl), dtype=dt, device=dev)
-            _, _, lse = ops.attn2_fwd(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], lqkv[:, :Hl], lqkv[:, Hl:2 * Hl], lqkv[:, 2 * Hl:],
-                                      B, nh, S, 1.0 / math.sqrt(d), 1.0 / math.sqrt(dl), st.key_bias, out_a=att, out_b=latt,
-                                      drop_p=seeds.p_attn, drop_words=seeds.attn_words(idx, cfg.num_hidden_layers, B, nh, S, dev))
-            if grouped:
-                xo, lo, sv_t, sv_l = _post_attn_fwd2(wc, idx, dt, cfg.layer_norm_eps, seeds, site + 2, site + 6, x, att, tp, l, latt, lp)
-            else:
-                xo, sv_t = _post_attn_fwd(wc, f"L{idx}.t", dt, cfg.layer_norm_eps, seeds, site + 2, x, att, tp)
-                lo, sv_l = _post_attn_fwd(wc, f"L{idx}.l", dt, cfg.layer_norm_eps, seeds, site + 6, l, latt, lp)
-            ctx.grouped = grouped
-            ctx.model, ctx.st, ctx.idx = model, st, idx
-            ctx.saved = (x, l, qkv, lqkv, lse, sv_t, sv_l)     # (att / latt are sv_t[0] / sv_l[0])
-            ctx.params = params
-            return xo, lo
-        cat = torch.empty((R, 3 * nh * dc), dtype=dt, device=dev)
-        ops.head_concat(qkv[:, :H], lqkv[:, :Hl], nh, cat[:, :nh * dc], 1.0 / math.sqrt(d), 1.0 / math.sqrt(dl))
-        ops.head_concat(qkv[:, H:], lqkv[:, Hl:], 2 * nh, cat[:, nh * dc:])      # k and v in one launch: 2 nh "heads"
-        qc, kc, vc = cat[:, :nh * dc], cat[:, nh * dc:2 * nh * dc], cat[:, 2 * nh * dc:]
-        attc, lse = ops.attn_fwd(qc, kc, vc, B, nh, S, dc, 1.0, None, st.key_bias, drop_p=seeds.p_attn,
-                                 drop_words=seeds.attn_words(idx, cfg.num_hidden_layers, B, nh, S, dev))
-        att = torch.empty((R, H), dtype=dt, device=dev)
-        latt = torch.empty((R, Hl), dtype=dt, device=dev)
-        ops.head_split(attc, nh, att, latt)
-        if grouped:
-            xo, lo, sv_t, sv_l = _post_attn_fwd2(wc, idx, dt, cfg.layer_norm_eps, seeds, site + 2, site + 6, x, att, tp, l, latt, lp)
-        else:
-            xo, sv_t = _post_attn_fwd(wc, f"L{idx}.t", dt, cfg.layer_norm_eps, seeds, site + 2, x, att, tp)
-            lo, sv_l = _post_attn_fwd(wc, f"L{idx}.l", dt, cfg.layer_norm_eps, seeds, site + 6, l, latt, lp)
-        ctx.grouped = grouped
-        ctx.model, ctx.st, ctx.idx = model, st, idx
-        ctx.saved = (x, l, cat, attc, lse, sv_t, sv_l)
+        qkv, lqkv = _gemms(route.grouped, [(x, Wqkv, dict(bias=bqkv)), (l, Wlqkv, dict(bias=blqkv))])    # [R, 3H], [R, 3Hl]
+        att, latt, kept = _ATTN_FWD[route.attention](cfg, st, idx, qkv, lqkv)
+        xo, lo, sv_t, sv_l = _post_attn_fwd(wc, idx, dt, cfg.layer_norm_eps, st.seeds, route.grouped, site + 2, site + 6,
+                                            x, att, tp, l, latt, lp)
+        ctx.model, ctx.st, ctx.idx, ctx.route = model, st, idx, route
+        ctx.saved = _LayerSaved(x, l, kept, sv_t, sv_l)
         ctx.params = params
         return xo, lo
 
     @staticmethod
     def backward(ctx, d_xo, d_lo):
-        model, st, idx = ctx.model, ctx.st, ctx.idx
+        model, st, idx, route = ctx.model, ctx.st, ctx.idx, ctx.route
         (wq, bq, wk, bk, wv, bv, lwq, lbq, lwk, lbk, lwv, lbv, *rest) = ctx.params
-        tp, lp = rest[:10], rest[10:]
-        x, l, cat, attc, lse, sv_t, sv_l = ctx.saved       # (st.attn2_train: qkv and lqkv where the concat path keeps cat and attc)
+        tp, lp = _PostParams(*rest[:10]), _PostParams(*rest[10:])
+        x, l, attn_kept, sv_t, sv_l = ctx.saved
         cfg, wc, dt = model.config, model.weight_cache, st.dtype
-        B, S = st.dims
-        H, nh = cfg.hidden_size, cfg.num_attention_heads
-        Hl = H // cfg.channel_shrink_ratio
-        d, dl = H // nh, Hl // nh
-        dc = d + dl
-        seeds = st.seeds
+        H, Hl = cfg.hidden_size, cfg.hidden_size // cfg.channel_shrink_ratio
         site = 32 * (idx + 1)
-        dev = x.device
-        R = x.shape[0]
         main = torch.cuda.current_stream()
-        side = model.side_stream(dev)
+        side = model.side_stream(x.device)
 
         # operand tensors of the side-stream work, referenced until the (deferred) join.  Only what the side stream READS:
         # a reference to one of its OUTPUTS (the bias-gradient slices are returned as gradients) would push that tensor's
@@ -443,53 +442,29 @@ class _LiltLayerStage(torch.autograd.Function):
                 side.wait_event(ev)
                 return fn()
 
-        wg_t = wg_l = None
-        if ctx.grouped:
-            d_att, d_x_res, gt, d_latt, d_l_res, gl, wg_t, wg_l = _post_attn_bwd2(wc, idx, dt, seeds, site + 2, site + 6, d_xo, d_lo, sv_t, sv_l, tp, lp, on_side)
-        else:
-            d_att, d_x_res, gt = _post_attn_bwd(wc, f"L{idx}.t", dt, seeds, site + 2, d_xo, sv_t, tp, on_side)
-            d_latt, d_l_res, gl = _post_attn_bwd(wc, f"L{idx}.l", dt, seeds, site + 6, d_lo, sv_l, lp, on_side)
-        dqkv = torch.empty((R, 3 * H), dtype=dt, device=dev)
-        dlqkv = torch.empty((R, 3 * Hl), dtype=dt, device=dev)
-        if st.attn2_train:
-            qkv, lqkv = cat, attc
-            ops.attn2_bwd(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], lqkv[:, :Hl], lqkv[:, Hl:2 * Hl], lqkv[:, 2 * Hl:],
-                          sv_t[0], d_att, sv_l[0], d_latt, lse, B, nh, S, 1.0 / math.sqrt(d), 1.0 / math.sqrt(dl), st.key_bias,
-                          dqkv, dlqkv, drop_p=seeds.p_attn,
-                          drop_words=seeds.attn_words(idx, cfg.num_hidden_layers, B, nh, S, dev))
-        else:
-            d_attc = torch.empty((R, nh * dc), dtype=dt, device=dev)
-            ops.head_concat(d_att, d_latt, nh, d_attc)
-            qc, kc, vc = cat[:, :nh * dc], cat[:, nh * dc:2 * nh * dc], cat[:, 2 * nh * dc:]
-            dcat = torch.empty_like(cat)
-            ops.attn_bwd(qc, kc, vc, attc, d_attc, lse, B, nh, S, dc, 1.0, None, st.key_bias, dcat, None, drop_p=seeds.p_attn,
-                         drop_words=seeds.attn_words(idx, cfg.num_hidden_layers, B, nh, S, dcat.device))
-            ops.head_split(dcat[:, :nh * dc], nh, dqkv[:, :H], dlqkv[:, :Hl], 1.0 / math.sqrt(d), 1.0 / math.sqrt(dl))
-            ops.head_split(dcat[:, nh * dc:], 2 * nh, dqkv[:, H:], dlqkv[:, Hl:])
+        d_att, d_x_res, gt, d_latt, d_l_res, gl, wg_t, wg_l = _post_attn_bwd(wc, idx, dt, st.seeds, route.grouped, site + 2, site + 6,
+                                                                             d_xo, d_lo, sv_t, sv_l, tp, lp, on_side)
+        dqkv = torch.empty((x.shape[0], 3 * H), dtype=dt, device=x.device)
+        dlqkv = torch.empty((x.shape[0], 3 * Hl), dtype=dt, device=x.device)
+        _ATTN_BWD[route.attention](cfg, st, idx, attn_kept, sv_t[0], sv_l[0], d_att, d_latt, dqkv, dlqkv)
         Wqkv = wc.cat_rows(f"L{idx}.qkv", [wq, wk, wv], dt)
         Wlqkv = wc.cat_rows(f"L{idx}.lqkv", [lwq, lwk, lwv], dt)
-        wg = lambda dy, xin: ops.gemm(dy, xin, a_kmajor=False, b_kmajor=False, out_dtype=torch.float32)
-        if ctx.grouped:
-            def all_wgrads():
-                gt_ = ops.gemm_group([(dqkv, x, None)] + [(dy, xin, None) for dy, xin in wg_t], a_kmajor=False, b_kmajor=False,
-                                     out_dtype=torch.float32)
-                gl_ = ops.gemm_group([(dlqkv, l, None)] + [(dy, xin, None) for dy, xin in wg_l], a_kmajor=False, b_kmajor=False,
-                                     out_dtype=torch.float32)
-                return ops.colsum(dqkv), ops.colsum(dlqkv), gt_, gl_
-            dbqkv, dblqkv, gt_, gl_ = on_side(all_wgrads, (dqkv, dlqkv, x, l) + tuple(t for pr in wg_t + wg_l for t in pr))
-            dwqkv, dwi_, dwo2_, dwo_ = gt_
-            dwlqkv, ldwi_, ldwo2_, ldwo_ = gl_
-            gt = (dwo_,) + gt[1:4] + (dwi_,) + gt[5:6] + (dwo2_,) + gt[7:]
-            gl = (ldwo_,) + gl[1:4] + (ldwi_,) + gl[5:6] + (ldwo2_,) + gl[7:]
-        else:
-            dbqkv, dblqkv, dwqkv, dwlqkv = on_side(lambda: (ops.colsum(dqkv), ops.colsum(dlqkv), wg(dqkv, x), wg(dlqkv, l)),
-                                                   (dqkv, dlqkv, x, l))
-        if ctx.grouped:
-            d_x, d_l = ops.gemm_group([(dqkv, Wqkv, None, dict(residual=d_x_res)), (dlqkv, Wlqkv, None, dict(residual=d_l_res))], b_kmajor=False)
-        else:
-            d_x = ops.gemm(dqkv, Wqkv, b_kmajor=False, residual=d_x_res)
-            d_l = ops.gemm(dlqkv, Wlqkv, b_kmajor=False, residual=d_l_res)
-        if os.environ.get("PENEO_DEFER_JOIN", "1") != "0" and can_defer(ctx.params):
+
+        # the QKV weight gradient and _post_attn_bwd's three, per stream: one grouped launch, else one split-k GEMM each
+        wgrads = lambda pairs: _gemms(route.grouped, [(dy, xin, {}) for dy, xin in pairs], a_kmajor=False, b_kmajor=False,
+                                      out_dtype=torch.float32)
+
+        def all_wgrads():
+            gt_ = wgrads([(dqkv, x)] + wg_t)
+            gl_ = wgrads([(dlqkv, l)] + wg_l)
+            return ops.colsum(dqkv), ops.colsum(dlqkv), gt_, gl_
+        dbqkv, dblqkv, gt_, gl_ = on_side(all_wgrads, (dqkv, dlqkv, x, l) + tuple(t for pr in wg_t + wg_l for t in pr))
+        dwqkv, dwi_, dwo2_, dwo_ = gt_
+        dwlqkv, ldwi_, ldwo2_, ldwo_ = gl_
+        gt = (dwo_,) + gt[1:4] + (dwi_,) + gt[5:6] + (dwo2_,) + gt[7:]
+        gl = (ldwo_,) + gl[1:4] + (ldwi_,) + gl[5:6] + (ldwo2_,) + gl[7:]
+        d_x, d_l = _gemms(route.grouped, [(dqkv, Wqkv, dict(residual=d_x_res)), (dlqkv, Wlqkv, dict(residual=d_l_res))], b_kmajor=False)
+        if route.defer_join and can_defer(ctx.params):
             defer_join(side, keep=kept)   # joined one stage later: the critical path does not wait for the QKV wgrads (engine.py)
         else:
             main.wait_stream(side)
@@ -541,7 +516,6 @@ class LiltModel(nn.Module):
 
     def side_stream(self, device) -> "torch.cuda.Stream":
         return engine_side_stream(device, "wgrad")
-
 
     def input_status(self, dev) -> torch.Tensor:
         """int32 [1] on `dev`, sticky: set to 1 by the layout embedding kernel when a box coordinate is out of range."""
@@ -601,9 +575,7 @@ class LiltModel(nn.Module):
         kb = torch.zeros((B, ops.attn_padded_len(S)), dtype=torch.float32, device=dev)
         kb[:, :S].masked_fill_(attention_mask == 0, -1.0e30)
         st.key_bias = kb
-        H, nh = cfg.hidden_size, cfg.num_attention_heads
-        st.attn2 = _use_attn2(st.dtype, st.seeds, H // nh, H // cfg.channel_shrink_ratio // nh)   # once per forward; the layers follow
-        st.attn2_train = _use_attn2_train(st.dtype, st.seeds, H // nh, H // cfg.channel_shrink_ratio // nh)
+        st.route = lilt_route(cfg, st.dtype, st.seeds, torch.is_grad_enabled())   # once per forward; the layers follow
         e, le = self.embeddings, self.layout_embeddings
         eparams = [e.word_embeddings.weight, e.token_type_embeddings.weight, e.position_embeddings.weight,
                    e.LayerNorm.weight, e.LayerNorm.bias, le.x_position_embeddings.weight, le.y_position_embeddings.weight,

@@ -34,26 +34,31 @@ def test_workspace_holds_delta_and_the_slab(lib):
         assert ctypes.c_ssize_t(lib.peneo_attn2_bwd_workspace_bytes(B, nh, T)).value <= 0
 
 
+def _lilt_cfg(size="base"):
+    from seeded import lilt_config
+    from peneo_amd.model.configuration_peneo import LiltConfig
+    return LiltConfig(**{k: v for k, v in lilt_config(size).items() if k != "model_type"})
+
+
 @pytest.mark.parametrize("value,on", [(None, False), ("0", False), ("", False), ("1", True)])
 def test_training_switch_is_off_unless_set_to_one(monkeypatch, value, on):
-    from peneo_amd.model import modeling_lilt as ml
+    from peneo_amd.model.modeling_lilt import lilt_route
     if value is None:
         monkeypatch.delenv("PENEO_LILT_ATTN2_TRAIN", raising=False)
     else:
         monkeypatch.setenv("PENEO_LILT_ATTN2_TRAIN", value)
     train = SimpleNamespace(p_attn=0.1)
-    with torch.enable_grad():
-        assert ml._use_attn2_train(torch.bfloat16, train, 64, 16) is on
+    assert (lilt_route(_lilt_cfg(), torch.bfloat16, train, True).attention == "attn2_train") is on
 
 
 def test_training_switch_needs_bf16_the_widths_and_a_training_forward(monkeypatch):
-    from peneo_amd.model import modeling_lilt as ml
+    from peneo_amd.model.modeling_lilt import lilt_route
     monkeypatch.setenv("PENEO_LILT_ATTN2_TRAIN", "1")
+    monkeypatch.delenv("PENEO_LILT_ATTN2", raising=False)
     train, evals = SimpleNamespace(p_attn=0.1), SimpleNamespace(p_attn=0.0)
-    with torch.enable_grad():
-        assert ml._use_attn2_train(torch.bfloat16, evals, 64, 16)             # autograd alone is enough
-        assert not ml._use_attn2_train(torch.float32, train, 64, 16)
-        assert not ml._use_attn2_train(torch.bfloat16, train, 48, 12)
-    with torch.no_grad():
-        assert ml._use_attn2_train(torch.bfloat16, train, 64, 16)             # attention dropout alone is enough
-        assert not ml._use_attn2_train(torch.bfloat16, evals, 64, 16)         # an eval forward: _use_attn2's business
+    base, tiny = _lilt_cfg(), _lilt_cfg("tiny")                                                  # head dims 64 + 16, 48 + 12
+    assert lilt_route(base, torch.bfloat16, evals, True).attention == "attn2_train"             # autograd alone is enough
+    assert lilt_route(base, torch.float32, train, True).attention != "attn2_train"
+    assert lilt_route(tiny, torch.bfloat16, train, True).attention != "attn2_train"
+    assert lilt_route(base, torch.bfloat16, train, False).attention == "attn2_train"            # attention dropout alone is enough
+    assert lilt_route(base, torch.bfloat16, evals, False).attention == "attn2_eval"             # an eval forward
