@@ -523,6 +523,27 @@ int peneo_pair_heads_fwd_mxfp8(const void* ab, int B, int N, const peneo_pair_he
                                float* const* logits /* host array of num_heads device pointers, or NULL */,
                                const peneo_pair_loss* loss, peneo_stream_t stream);
 
+/* MXFP8 inference form of the heads at decoder widths 512 < D <= 1024 (version 112; pair_heads_mx_wide.hip): the contract of
+ * peneo_pair_heads_fwd_mxfp8 above, word for word - the same quantizer on both first-layer operands, the scaled MFMAs in the same
+ * k-step order, + b1, SiLU, the bf16 second layer, + b2, fp32 logits, the loss rows of 256 pairs (`loss->partials` has
+ * peneo_pair_loss_partials(B, N) rows; single-writer, no atomics, no workspace, no allocation) - on a kernel of its own: four waves
+ * that hold two groups of 32 pairs each, so that 256 pairs share one pass over every weight slab.  The narrow entry points keep
+ * answering exactly as before (0 / PENEO_ERR_INVALID above D = 512).
+ * peneo_pair_mxfp8_wide_supported: host-side query (no GPU call): 1 when D % 64 == 0, 512 < D <= 1024, 1 <= num_heads <=
+ * PENEO_MAX_HEADS and the ring of three weight slabs + the b1 table fit in 160 KiB of LDS (true for every such D up to 8 heads), else 0.
+ * peneo_pair_heads_pack_mxfp8_wide: as peneo_pair_heads_pack_mxfp8 -> `packed` [peneo_pair_heads_mxfp8_wide_packed_bytes]
+ * (16-byte aligned; 0 bytes = unsupported shape): the same slab contents at a stride of a whole number of 4 KiB.  The two packs are
+ * not interchangeable; a pointer carries no size, so a wrong one is NOT detectable.
+ * peneo_pair_heads_fwd_mxfp8_wide: the arguments of peneo_pair_heads_fwd_mxfp8 with w_packed from the pack above.  PENEO_ERR_INVALID
+ * with a peneo_last_error() text naming the argument: drop_p != 0, a non-NULL dlogits[h], a (D, num_heads) the query refuses. */
+int peneo_pair_mxfp8_wide_supported(int D, int num_heads);
+size_t peneo_pair_heads_mxfp8_wide_packed_bytes(int num_heads, int D);
+int peneo_pair_heads_pack_mxfp8_wide(const float* const* w1, const float* const* w2, const int* classes, int num_heads, int D,
+                                     void* packed, peneo_stream_t stream);
+int peneo_pair_heads_fwd_mxfp8_wide(const void* ab, int B, int N, const peneo_pair_heads_desc* desc,
+                                    float* const* logits /* host array of num_heads device pointers, or NULL */,
+                                    const peneo_pair_loss* loss, peneo_stream_t stream);
+
 /* MXFP8 train forward of the same heads (version 105): the first layer of peneo_pair_heads_fwd_mxfp8 - same quantizer, same scaled
  * MFMAs in the same order - on the walk of peneo_pair_heads_fwd_save, leaving what peneo_pair_bwd_saved reads.
  * peneo_pair_mxfp8_save_supported: host-side query (no GPU call): 1 exactly when peneo_pair_save_supported(PENEO_BF16, D, num_heads)

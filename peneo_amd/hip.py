@@ -191,6 +191,10 @@ SIGNATURES = {
     "peneo_pair_heads_mxfp8_packed_bytes": (_sz, [_i, _i]),
     "peneo_pair_heads_pack_mxfp8": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
     "peneo_pair_heads_fwd_mxfp8": (_i, [_vp, _i, _i, C.POINTER(PairHeadsDesc), _vp, C.POINTER(PairLoss), _vp]),
+    "peneo_pair_mxfp8_wide_supported": (_i, [_i, _i]),
+    "peneo_pair_heads_mxfp8_wide_packed_bytes": (_sz, [_i, _i]),
+    "peneo_pair_heads_pack_mxfp8_wide": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "peneo_pair_heads_fwd_mxfp8_wide": (_i, [_vp, _i, _i, C.POINTER(PairHeadsDesc), _vp, C.POINTER(PairLoss), _vp]),
     "peneo_pair_mxfp8_save_supported": (_i, [_i, _i]),
     "peneo_pair_heads_fwd_mxfp8_save": (_i, [_vp, _i, _i, C.POINTER(PairHeadsDesc), _vp, C.POINTER(PairLoss), _vp, _vp, _vp]),
     "peneo_pair_bwd_saved": (_i, [_i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -175,13 +175,14 @@ class PEneoModel(PEneoPreTrainedModel):
         self.backbone.compute_dtype = dtype
         return self
 
-    def set_pair_heads_format(self, fmt: str) -> "PEneoModel":
+    def set_pair_heads_format(self, fmt: str, *, wide: bool = False) -> "PEneoModel":
         """"bf16" (default) or "mxfp8": the MXFP8 inference path of the five pair classifiers (eval forwards without
         gradients only; a forward with gradients raises ValueError).  "mxfp8" needs compute dtype torch.bfloat16, 2-layer
-        classifiers and a decoder width the kernel supports; otherwise this raises ValueError."""
+        classifiers and a decoder width the kernel supports - up to 512, with ``wide=True`` also the shrink-off widths up to 1024
+        (PEneoDecoder.set_pair_heads_format); otherwise this raises ValueError."""
         if fmt == "mxfp8" and self._compute_dtype != torch.bfloat16:
             raise ValueError("mxfp8 pair heads need set_compute_dtype(torch.bfloat16) first")
-        self.peneo_decoder.set_pair_heads_format(fmt)
+        self.peneo_decoder.set_pair_heads_format(fmt, wide=wide)
         return self
 
     def set_pair_heads_train_format(self, fmt: str) -> "PEneoModel":

@@ -221,7 +221,10 @@ def pair_route(dec: "PEneoDecoder", dt: torch.dtype, D: int, need_grad: bool, ha
     forward received an attention mask (what skip_padded_pairs takes the lengths from)."""
     nh = len(HEAD_NAMES)
     train = need_grad and has_tags
-    if not dec.fused_pair_heads(dt, D):
+    # (above 512 the "mxfp8" format - set_pair_heads_format("mxfp8", wide=True) - has a kernel of its own and does not consult
+    # pair_wide, the bf16 A/B arm inside fused_pair_heads; up to 512 the order of the questions is what it always was)
+    mx_wide = dec.pair_heads_format == "mxfp8" and D > 512
+    if not mx_wide and not dec.fused_pair_heads(dt, D):
         # (classifier depths other than the shipped 2, widths without a fused pair-heads kernel: the materialising per-document path)
         return PairRoute("generic", backward="generic" if train else None)
     if dec.pair_heads_format == "mxfp8":
@@ -328,6 +331,14 @@ class _DecoderStage(torch.autograd.Function):
             [w.detach() for w in w1s], [w.detach() for w in w2s]))
         if route.forward == "mxfp8_eval":
             assert not need_grad
+            if D > 512:
+                # (set_pair_heads_format("mxfp8", wide=True): the four-wave kernel, its own pack and cache key; the width picks
+                # the op as it does on the "bf16" route, and pair_wide - the bf16 A/B arm - is not consulted)
+                wpw = wc.get(("dec.pack_mxfp8_wide",), w1s + w2s, lambda: ops.pair_heads_pack_mxfp8_wide(
+                    [w.detach() for w in w1s], [w.detach() for w in w2s]))
+                res = ops.pair_heads_fwd_mxfp8_wide(ab, wpw, b1cat, b2cat, HEAD_CLASSES, want_logits=want_logits, tags=tags,
+                                                    class_weights=cws)
+                return _DecoderStage._finish(ctx, res, tags, cws)
             res = ops.pair_heads_fwd_mxfp8(ab, pack_mxfp8(), b1cat, b2cat, HEAD_CLASSES, want_logits=want_logits, tags=tags,
                                            class_weights=cws)
             return _DecoderStage._finish(ctx, res, tags, cws)
@@ -839,17 +850,22 @@ class PEneoDecoder(nn.Module):
         #     15.19 ms per step against 15.67 / 15.51 / 15.46 at split 5 / 7 / 8 and 15.79 on the 128 x 128 kernel, profiles/r07_dw1_nn384.txt)
         self._ratio = {}
 
-    def set_pair_heads_format(self, fmt: str) -> None:
+    def set_pair_heads_format(self, fmt: str, *, wide: bool = False) -> None:
         """"bf16" (default): the pair heads run in the compute dtype.  "mxfp8": eval forwards (no gradients) run the first
         layer of the five classifiers on block-scaled e4m3 (include/peneo_hip.h, peneo_pair_heads_fwd_mxfp8); a forward with
-        gradients raises.  Needs the 2-layer classifiers and a decoder width the kernel holds."""
+        gradients raises.  Needs the 2-layer classifiers and a decoder width the kernel holds: up to 512, and with ``wide=True``
+        also 512 < D <= 1024 (the decoder shrink off: peneo_pair_heads_fwd_mxfp8_wide, same numeric contract).  ``wide`` changes
+        nothing at D <= 512."""
         if fmt not in ("bf16", "mxfp8"):
             raise ValueError(f"unknown pair-heads format {fmt!r} (expected 'bf16' or 'mxfp8')")
         if fmt == "mxfp8":
+            D, nh = self.decoder_hidden_size, len(HEAD_NAMES)
             if self.num_cls_layers != 2:
                 raise ValueError(f"mxfp8 pair heads need peneo_classifier_num_layers == 2, not {self.num_cls_layers}")
-            if not ops.pair_mxfp8_supported(self.decoder_hidden_size, len(HEAD_NAMES)):
-                raise ValueError(f"mxfp8 pair heads do not support decoder width D = {self.decoder_hidden_size}")
+            if not (ops.pair_mxfp8_supported(D, nh) or (wide and ops.pair_mxfp8_wide_supported(D, nh))):
+                hint = "" if wide or not ops.pair_mxfp8_wide_supported(D, nh) else \
+                    " (above 512 the kernel is opt-in: set_pair_heads_format('mxfp8', wide=True))"
+                raise ValueError(f"mxfp8 pair heads do not support decoder width D = {D}{hint}")
             if self.skip_padded_pairs:
                 raise ValueError("the mxfp8 pair heads have no length-aware form: switch set_skip_padded_pairs(False) first")
         self.pair_heads_format = fmt

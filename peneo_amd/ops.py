@@ -1098,6 +1098,40 @@ def pair_heads_fwd_mxfp8(ab: torch.Tensor, wp: torch.Tensor, b1: torch.Tensor, b
                               class_weights)
 
 
+def pair_mxfp8_wide_supported(D: int, num_heads: int) -> bool:
+    """True when the wide MXFP8 pair-heads kernel holds this shape (host-side, no GPU call): D % 64 == 0, 512 < D <= 1024."""
+    return bool(lib().peneo_pair_mxfp8_wide_supported(int(D), int(num_heads)))
+
+
+def pair_heads_pack_mxfp8_wide(w1: Sequence[torch.Tensor], w2: Sequence[torch.Tensor]) -> torch.Tensor:
+    """pair_heads_pack_mxfp8 for 512 < D <= 1024: the packed buffer of pair_heads_fwd_mxfp8_wide (a pack of its own)."""
+    nh, D = len(w1), w1[0].shape[1]
+    nbytes = lib().peneo_pair_heads_mxfp8_wide_packed_bytes(nh, D)
+    if nbytes == 0:
+        raise ValueError(f"wide MXFP8 pair heads: D={D} with {nh} heads is not supported")
+    packed = torch.empty(nbytes, dtype=torch.uint8, device=w1[0].device)
+    classes = (C.c_int * nh)(*[w.shape[0] for w in w2])
+    check(lib().peneo_pair_heads_pack_mxfp8_wide(_ptr_list([_c(w) for w in w1]), _ptr_list([_c(w) for w in w2]), classes, nh, D,
+                                                 ptr(packed), stream()), "peneo_pair_heads_pack_mxfp8_wide")
+    return packed
+
+
+def pair_heads_fwd_mxfp8_wide(ab: torch.Tensor, wp: torch.Tensor, b1: torch.Tensor, b2: torch.Tensor,
+                              classes: Sequence[int], *, want_logits: bool = True, tags: Optional[Sequence[torch.Tensor]] = None,
+                              class_weights: Optional[Sequence[Optional[torch.Tensor]]] = None):
+    """pair_heads_fwd_mxfp8 for 512 < D <= 1024: ab [B, N, 2D] bf16, wp from pair_heads_pack_mxfp8_wide.
+    Returns (logits list | None, loss partials [n, 32] | None, None) like pair_heads_fwd without dlogits."""
+    _c(ab)
+    assert ab.dtype == torch.bfloat16, "pair_heads_fwd_mxfp8_wide takes bf16 ab"
+    D, nh = ab.shape[2] // 2, len(classes)
+    if not pair_mxfp8_wide_supported(D, nh):
+        raise ValueError(f"wide MXFP8 pair heads: D={D} with {nh} heads is not supported")
+    if wp.dtype != torch.uint8 or wp.numel() != lib().peneo_pair_heads_mxfp8_wide_packed_bytes(nh, D):
+        raise ValueError("pair_heads_fwd_mxfp8_wide: wp is not a pair_heads_pack_mxfp8_wide buffer for this shape")
+    return _pair_heads_launch("peneo_pair_heads_fwd_mxfp8_wide", "pair_heads_fwd_mxfp8_wide", ab, wp, b1, b2, classes, want_logits,
+                              tags, class_weights)
+
+
 def pair_mxfp8_save_supported(D: int, num_heads: int) -> bool:
     """True when pair_heads_fwd_mxfp8_save exists for this shape: the saved backward and the MXFP8 kernel both hold it (D = 384)."""
     return bool(lib().peneo_pair_mxfp8_save_supported(int(D), int(num_heads)))
