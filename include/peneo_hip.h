@@ -250,6 +250,24 @@ int peneo_relpos_buckets(const int32_t* pos, const int32_t* xs, const int32_t* y
                          const uint8_t* lut1, int lut1_len, int half1,
                          const uint8_t* lut2, int lut2_len, int half2,
                          uint8_t* bk1, uint8_t* bkx, uint8_t* bky, peneo_stream_t stream);
+/* Packed ("varlen") inference, the row movers (version 113; csrc/rows_pack.hip).  Every buffer is the caller's; nothing is allocated.
+ * peneo_pack_plan: order-preserving compaction of key_mask int32 [B, T] (peneo_relpos_inputs; holes allowed), per document:
+ *   lens [B] = number of non-zero entries of row b; cu_rows [B + 1] = their exclusive prefix sum (cu_rows[B] = all live rows);
+ *   live_t [B, T]: live_t[b, i] = position of the i-th non-zero entry of row b, ascending, and -1 for i >= lens[b].
+ *   One launch, no atomics, no workspace.
+ * peneo_rows_pack: gathers rows of `row_bytes` bytes (a multiple of 4; contiguous rows) out of src [B, T, row_bytes]:
+ *   cu_rows given: dst row cu_rows[b] + i = src row (b, live_t[b, i]) for i < min(lens[b], Tm) (dst has dst_rows rows; a row outside
+ *     it is not written; rows of dst that belong to no live token are left alone);
+ *   cu_rows NULL: the per-document layout dst [B, Tm, row_bytes], dst_rows = B * Tm: row (b, i) as above for i < lens[b], zeros from
+ *     lens[b] on - every row is written (the int32 pos / xs / ys inputs of peneo_relpos_buckets at T = Tm).
+ * peneo_rows_unpack: the inverse of the cu_rows layout: writes EVERY row of dst [B, T, row_bytes] - row (b, live_t[b, i]) = src row
+ *   cu_rows[b] + i (src has src_rows rows), all other rows zeros.  live_t rows must be ascending, as peneo_pack_plan writes them.
+ * Rows move as 16-byte pieces when row_bytes and both base pointers are multiples of 16, else as dwords (4-byte alignment is required). */
+int peneo_pack_plan(const int32_t* key_mask, int B, int T, int32_t* lens, int32_t* cu_rows, int32_t* live_t, peneo_stream_t stream);
+int peneo_rows_pack(const void* src, const int32_t* live_t, const int32_t* lens, const int32_t* cu_rows, int B, int T, int Tm,
+                    int64_t row_bytes, void* dst, int64_t dst_rows, peneo_stream_t stream);
+int peneo_rows_unpack(const void* src, int64_t src_rows, const int32_t* live_t, const int32_t* lens, const int32_t* cu_rows, int B, int T,
+                      int64_t row_bytes, void* dst, peneo_stream_t stream);
 /* bias[b,h,i,j] = scale * (w1[h,bk1] + wx[h,bkx] + wy[h,bky]); any of the three may be NULL.
  * Output layout [B, nh, T, Tp] with Tp = peneo_attn_padded_len(T); columns j >= T and keys with
  * key_mask[b,j] == 0 (may be NULL) hold -1e30, which is how the attention kernels see the padding mask. */
@@ -291,10 +309,28 @@ int peneo_head_transpose(int dtype, const void* src, int64_t ld, int B, int nh, 
                          peneo_stream_t stream);
 /* v / vt: bf16 takes V in place (row stride ld_qk, like q and k) and reads V^T with the hardware transpose read, vt may
  * be NULL; fp32 needs vt, the per-head transposed copy from peneo_head_transpose (v is then ignored). */
+/* bias_ld: peneo_attn_padded_len(T); since version 113 the forward also takes a larger row stride that is a multiple of 8 (the rows
+ * of one document cut out of a bias tensor built for a longer one): the kernels read columns below peneo_attn_padded_len(T) only. */
 int peneo_attn_fwd(int dtype, const void* q, const void* k, const void* v, int64_t ld_qk, const void* vt,
                    int B, int nh, int T, int d, float scale, const void* bias, int64_t bias_ld,
                    const float* key_bias, void* out, int64_t ld_out, float* lse, float drop_p, const uint32_t* drop_words,
                    peneo_stream_t stream);
+/* Per-document-length ("varlen") form of the forward for packed inference (version 113; csrc/attn_fwd_pipe.hip).  It covers the
+ * shape the pipelined kernel covers: bf16, d = 64, bias tensor present, V row-major, no dropout, no key_bias.
+ *   lens int32 [B], cu_rows int32 [B + 1] (peneo_pack_plan); Tm: the extent the grid, bias and lse are laid out for (>= max lens).
+ *   q / k / v / out: `rows` rows in all; the rows of document b are cu_rows[b] .. cu_rows[b] + n_b - 1, n_b = min(lens[b], Tm).
+ *   bias [B, nh, Tm, bias_ld] (bias_ld a multiple of 8, >= Tm rounded up to 32); lse fp32 [B, nh, Tm] (may be NULL).
+ * For every document, out and lse rows below n_b hold what peneo_attn_fwd writes for that document alone (B = 1, T = n_b, its slice of
+ * the bias with the same bias_ld), bit for bit; keys from n_b on are never read into the softmax, whatever the bias holds there.  Rows
+ * from n_b on in lse, and every row of out that belongs to no document, are NOT written.  lens[b] <= 0 is legal: nothing is written for
+ * that document.  A document whose rows do not lie inside [0, rows) is skipped whole (nothing read, nothing written).
+ * peneo_attn_fwd_varlen_supported is a host-side question (no GPU call): 1 for (PENEO_BF16, 64), 0 for everything else.  An unsupported
+ * pair, a NULL operand / bias / lens / cu_rows, operands that are not 16-byte aligned or whose row strides are not whole 16-byte
+ * pieces, or a bias_ld too small return PENEO_ERR_INVALID with a peneo_last_error text, nothing launched - never a fallback. */
+int peneo_attn_fwd_varlen_supported(int dtype, int d);
+int peneo_attn_fwd_varlen(int dtype, const void* q, const void* k, const void* v, int64_t ld_qk, int64_t rows, const int32_t* lens,
+                          const int32_t* cu_rows, int B, int nh, int Tm, int d, float scale, const void* bias, int64_t bias_ld,
+                          void* out, int64_t ld_out, float* lse, peneo_stream_t stream);
 void peneo_attn_drop_words_dims(int T, int* n_query_blocks, int* n_key_slots);
 int64_t peneo_attn_drop_words_count(int B, int nh, int T);   /* = B * nh * n_query_blocks * n_key_slots */
 int peneo_attn_drop_words(uint32_t* words, int B, int nh, int T, float drop_p, uint32_t seed, peneo_stream_t stream);
@@ -813,6 +849,15 @@ size_t peneo_struct_bytes(int which);
 size_t peneo_encoder_layer_workspace_bytes(int rows, int H, int I, int which);
 int peneo_encoder_layer_fwd(const peneo_encoder_layer* layer, void* out, void* workspace, size_t workspace_bytes,
                             peneo_stream_t stream);
+/* Packed inference form of peneo_encoder_layer_fwd (version 113; no backward): the same chain over the `rows` live rows of a batch
+ * whose tokens were packed to the front (peneo_pack_plan, peneo_rows_pack) - every GEMM and LayerNorm at M = rows, the attention
+ * peneo_attn_fwd_varlen with lens / cu_rows.  `layer` as above with these readings: T is Tm, the extent of bias [B, nh, Tm, bias_ld] and
+ * lse [B, nh, Tm]; x, qkv, att, h1, a, inter, h2, out and m*, r* have `rows` rows; 1 <= rows <= B * T.  It requires p_hidden == p_attn ==
+ * 0, zi == NULL, a bias tensor, no key_bias and head dim 64, else PENEO_ERR_INVALID with nothing launched.  Workspace:
+ * peneo_encoder_layer_workspace_bytes(rows, H, I, 0).  With every lens[b] == T (rows = B * T) the result equals peneo_encoder_layer_fwd
+ * bit for bit. */
+int peneo_encoder_layer_fwd_packed(const peneo_encoder_layer* layer, const int32_t* lens, const int32_t* cu_rows, int rows, void* out,
+                                   void* workspace, size_t workspace_bytes, peneo_stream_t stream);
 /* MXFP8 inference form of peneo_encoder_layer_fwd (no backward): the four nn.Linear products run on peneo_gemm_mxfp8, attention and
  * the two LayerNorms stay bf16.  `layer` as above, except that Wqkv / Wo / Wi / Wo2, inter and zi are not used (zi must be NULL) and
  * p_hidden == p_attn == 0; `mx` carries the weights quantized with peneo_mxfp8_quantize_rows (W*_q [out, in] e4m3, W*_s [out, in / 32]

@@ -54,5 +54,5 @@ extern "C" void peneo_set_deterministic(int mode) { peneo::g_det_mode = mode < 0
 extern "C" int peneo_deterministic(void) { return peneo::det_mode(); }
 extern "C" uint64_t peneo_order_dependent_launches(void) { return peneo::g_order_dependent.load(std::memory_order_relaxed); }
 
-extern "C" int peneo_version(void) { return 112; }
+extern "C" int peneo_version(void) { return 113; }
 extern "C" const char* peneo_last_error(void) { return peneo::g_err; }

@@ -15,6 +15,8 @@ struct AttnParams {
   float drop_p, keep_scale; const uint32_t* words; int nqb, Tk;   // dropout keep bits (peneo_attn_drop_words) or NULL
   const void* d_out; void* dq; void* dk; void* dv; int64_t ld_d; float* g_bias; float* delta;
   void* ds_out;   // single-pass backward only: bf16 dS^T [B, nh, T keys, Tp queries] of this layer (or NULL)
+  // peneo_attn_fwd_varlen only (else NULL / 0): per-document lengths, first rows, and the row count of q / k / v / out; T is then Tm
+  const int32_t* lens; const int32_t* cu_rows; int rows;
 };
 
 // slot of a key's dropout keep word inside its 32-key block (see the note on the keep words in attention.hip): slots 2r and 2r + 1
@@ -28,7 +30,8 @@ __host__ __device__ __forceinline__ int attn_kslot(int key) {
 // (returns 0; or 1 when the caller still has to launch attn_dq_from_ds_kernel: PENEO_ATTN_DQ_PIPE=0).
 bool attn_bwd_pipe_supported(const AttnParams& p);
 int launch_attn_bwd_pipe(const AttnParams& p, hipStream_t st);
-// attn_fwd_pipe.hip: the pipelined forward (bf16, head dim 64, bias tensor, V row-major), bit-identical to attn_fwd_kernel
+// attn_fwd_pipe.hip: the pipelined forward (bf16, head dim 64, bias tensor, V row-major), bit-identical to attn_fwd_kernel;
+// with p.lens set the launcher starts the per-document-length form (peneo_attn_fwd_varlen, same file)
 bool attn_fwd_pipe_supported(const AttnParams& p);
 int launch_attn_fwd_pipe(const AttnParams& p, hipStream_t st);
 

@@ -1377,12 +1377,16 @@ extern "C" int peneo_head_transpose(int dtype, const void* src, int64_t ld, int 
   return check_launch("peneo_head_transpose");
 }
 
-static int attn_common_check(const char* who, int dtype, int B, int nh, int T, int d, const void* bias, int64_t bias_ld) {
+// wider_ld (version 113, the forward only: its kernels address the bias by bias_ld alone): a row stride above the padded length is
+// taken too, in whole 16-byte pieces - the rows of one document cut out of a bias tensor built for a longer one
+static int attn_common_check(const char* who, int dtype, int B, int nh, int T, int d, const void* bias, int64_t bias_ld,
+                             bool wider_ld = false) {
   PENEO_REQUIRE(dtype == PENEO_F32 || dtype == PENEO_BF16, "%s: bad dtype", who);
   PENEO_REQUIRE(B > 0 && nh > 0 && T > 0 && d > 0 && d <= 128, "%s: bad sizes", who);
   if (bias) {
-    PENEO_REQUIRE(bias_ld == peneo_attn_padded_len(T), "%s: bias row stride must be peneo_attn_padded_len(T) = %d", who,
-                  peneo_attn_padded_len(T));
+    const int Tp = peneo_attn_padded_len(T);
+    PENEO_REQUIRE(bias_ld == Tp || (wider_ld && bias_ld > Tp && bias_ld % 8 == 0), "%s: bias row stride must be peneo_attn_padded_len(T) = %d%s",
+                  who, Tp, wider_ld ? ", or above it and a multiple of 8" : "");
     PENEO_REQUIRE((reinterpret_cast<uintptr_t>(bias) & 15) == 0, "%s: bias must be 16-byte aligned", who);
   }
   return PENEO_OK;
@@ -1416,7 +1420,7 @@ static void set_drop(AttnParams& p, float drop_p, const uint32_t* words) {
 extern "C" int peneo_attn_fwd(int dtype, const void* q, const void* k, const void* v, int64_t ld_qk, const void* vt, int B, int nh, int T,
                               int d, float scale, const void* bias, int64_t bias_ld, const float* key_bias, void* out,
                               int64_t ld_out, float* lse, float drop_p, const uint32_t* drop_words, peneo_stream_t stream) {
-  int rc = attn_common_check("peneo_attn_fwd", dtype, B, nh, T, d, bias, bias_ld);
+  int rc = attn_common_check("peneo_attn_fwd", dtype, B, nh, T, d, bias, bias_ld, true);
   if (rc) return rc;
   PENEO_REQUIRE(q && k && out && (vt || (v && dtype == PENEO_BF16)), "peneo_attn_fwd: null pointer (fp32 needs the transposed copy vt)");
   PENEO_REQUIRE(ld_qk >= (int64_t)nh * d && ld_out >= (int64_t)nh * d, "peneo_attn_fwd: leading dims too small");

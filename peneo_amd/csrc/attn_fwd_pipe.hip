@@ -12,6 +12,13 @@
 //   * keys past T: K / V rows are clamped to T - 1 and the ragged last tile masks its scores itself (round 6: one wave-uniform branch
 //     per launch; until then the kernel relied on -1e30 in the bias tensor's padding columns, which peneo_attn_fwd does not promise);
 //   * O rows leave as 16-byte pieces straight from the accumulator layout (v_permlane32_swap pairs), no LDS round trip.
+//
+// VARLEN (version 113; peneo_attn_fwd_varlen): the per-document-length form for packed inference.  The grid, the bias [B, nh, Tm,
+// bias_ld] and lse [B, nh, Tm] are laid out for Tm = p.T; the q / k / v / out rows of document b start at row cu_rows[b] and there are
+// Tn = min(lens[b], Tm) of them.  A workgroup whose query block starts at or past Tn - or whose document does not lie inside the
+// caller's `rows` - returns before its first load, DMA or barrier; the test is on values every lane of all four waves holds alike
+// (blockIdx, kernel arguments, lens[b] and cu_rows[b]), so a workgroup leaves whole or not at all.  Every other workgroup runs the tile
+// loop below with that Tn, which is what the fixed-length kernel does for B = 1, T = Tn: the same bits.
 #include "common.h"
 #include "attention.h"
 #include "attn_pipe.h"
@@ -26,23 +33,31 @@ constexpr int O_K = 0, O_V = 4096, O_BIAS = 8192, O_WORDS = 16384, BUF = 17408;
 constexpr int NBUF = 3;
 constexpr int LDS_BYTES = NBUF * BUF;
 
-template <bool DROP>
+template <bool DROP, bool VARLEN>
 __global__ __launch_bounds__(256, 2) void attn_fwd_pipe_kernel(AttnParams p) {
+  static_assert(!(DROP && VARLEN), "the per-document-length form has no dropout");
   typedef bf16_t T;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, l31 = lane & 31;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int Tn = p.T;
+  const int Tm = p.T;                                // the extent the grid, the bias and lse are laid out for
   // unit order: the query blocks of one (document, head) run on ONE XCD (they stream the same K / V rows through its L2)
-  const int nqb = (Tn + WQ - 1) / WQ;
+  const int nqb = (Tm + WQ - 1) / WQ;
   const int u = xcd_unit();
   const int qb = u % nqb, bh = u / nqb, h = bh % p.nh, b = bh / p.nh;
   const int q0 = qb * WQ;
+  int Tn = Tm;                                       // keys = queries of this document
+  int64_t row0 = (int64_t)b * Tm;                    // its first row in q / k / v / out
+  if constexpr (VARLEN) {
+    Tn = min(__builtin_amdgcn_readfirstlane(p.lens[b]), Tm);
+    row0 = __builtin_amdgcn_readfirstlane(p.cu_rows[b]);
+    if (q0 >= Tn || row0 < 0 || row0 + Tn > p.rows) return;   // workgroup-uniform, before any DMA or barrier
+  }
   const int myq = q0 + wave * 32 + l31;
-  const T* Q = reinterpret_cast<const T*>(p.q) + (int64_t)b * Tn * p.ld + h * 64;
-  const T* K = reinterpret_cast<const T*>(p.k) + (int64_t)b * Tn * p.ld + h * 64;
-  const T* V = reinterpret_cast<const T*>(p.v) + (int64_t)b * Tn * p.ld + h * 64;
-  const T* bias = reinterpret_cast<const T*>(p.bias) + (int64_t)bh * Tn * p.bias_ld;
+  const T* Q = reinterpret_cast<const T*>(p.q) + row0 * p.ld + h * 64;
+  const T* K = reinterpret_cast<const T*>(p.k) + row0 * p.ld + h * 64;
+  const T* V = reinterpret_cast<const T*>(p.v) + row0 * p.ld + h * 64;
+  const T* bias = reinterpret_cast<const T*>(p.bias) + (int64_t)bh * Tm * p.bias_ld;
   const float keep_scale = DROP ? p.keep_scale : 1.0f;
   const int nt = (Tn + TK - 1) / TK;
 
@@ -229,9 +244,9 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_pipe_kernel(AttnParams p) {
   // ---- normalise; O rows: accumulator = [d rows (registers)][query (lane)], two groups + a v_permlane32_swap = 16 bytes per lane ----
   const bool any = m_run > 0.5f * kMasked;
   const float inv = (any && l_run > 0.f) ? keep_scale / l_run : 0.f;
-  if (half == 0 && myq < Tn && p.lse) p.lse[(int64_t)bh * Tn + myq] = any ? fmaf(m_run, kLog2e, log2f(l_run)) : kMasked;   // log2 units
+  if (half == 0 && myq < Tn && p.lse) p.lse[(int64_t)bh * Tm + myq] = any ? fmaf(m_run, kLog2e, log2f(l_run)) : kMasked;   // log2 units
   if (myq < Tn) {
-    T* dst = reinterpret_cast<T*>(p.out) + ((int64_t)b * Tn + myq) * p.ld_out + h * 64;
+    T* dst = reinterpret_cast<T*>(p.out) + (row0 + myq) * p.ld_out + h * 64;
 #pragma unroll
     for (int t2 = 0; t2 < 2; ++t2)
 #pragma unroll
@@ -241,14 +256,19 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_pipe_kernel(AttnParams p) {
 
 }  // namespace
 
-bool attn_fwd_pipe_supported(const AttnParams& p) {
-  static const bool on = env_switch_on("PENEO_ATTN_FWD_PIPE");
+// what the kernel needs of a call, in either form
+static bool pipe_operands_ok(const AttnParams& p) {
   auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  return on && p.d == 64 && p.bias != nullptr && p.key_bias == nullptr && p.vt == nullptr && p.v != nullptr &&
+  return p.d == 64 && p.bias != nullptr && p.key_bias == nullptr && p.vt == nullptr && p.v != nullptr &&
          al16(p.q) && al16(p.k) && al16(p.v) && al16(p.out) && al16(p.bias) &&
          (p.ld * 2) % 16 == 0 && (p.ld_out * 2) % 16 == 0 && (p.bias_ld * 2) % 16 == 0 && p.bias_ld >= 32 &&
          (int64_t)p.ld * 2 * 32 < (1ll << 31) && (int64_t)p.bias_ld * 2 * 128 < (1ll << 31) &&
          (p.T + TK - 1) / TK * TK <= (int)p.bias_ld;       // (whole 32-key tiles inside the padded bias row)
+}
+
+bool attn_fwd_pipe_supported(const AttnParams& p) {
+  static const bool on = env_switch_on("PENEO_ATTN_FWD_PIPE");
+  return on && pipe_operands_ok(p);
 }
 
 int launch_attn_fwd_pipe(const AttnParams& p, hipStream_t st) {
@@ -258,7 +278,35 @@ int launch_attn_fwd_pipe(const AttnParams& p, hipStream_t st) {
     hipLaunchKernelGGL(kern, grid, dim3(256), LDS_BYTES, st, p);
     return check_launch("peneo_attn_fwd(pipe)");
   };
-  return p.drop_p > 0.f ? go(attn_fwd_pipe_kernel<true>) : go(attn_fwd_pipe_kernel<false>);
+  if (p.lens) return go(attn_fwd_pipe_kernel<false, true>);
+  return p.drop_p > 0.f ? go(attn_fwd_pipe_kernel<true, false>) : go(attn_fwd_pipe_kernel<false, false>);
 }
 
 }  // namespace peneo
+
+using namespace peneo;
+
+extern "C" int peneo_attn_fwd_varlen_supported(int dtype, int d) { return dtype == PENEO_BF16 && d == 64; }
+
+extern "C" int peneo_attn_fwd_varlen(int dtype, const void* q, const void* k, const void* v, int64_t ld_qk, int64_t rows, const int32_t* lens,
+                                     const int32_t* cu_rows, int B, int nh, int Tm, int d, float scale, const void* bias, int64_t bias_ld,
+                                     void* out, int64_t ld_out, float* lse, peneo_stream_t stream) {
+  const char* const who = "peneo_attn_fwd_varlen";
+  PENEO_REQUIRE(peneo_attn_fwd_varlen_supported(dtype, d),
+                "%s: no kernel for dtype %d, d=%d (peneo_attn_fwd_varlen_supported: bf16, d = 64 only; there is no fallback)", who, dtype, d);
+  PENEO_REQUIRE(q && k && v && out && lens && cu_rows, "%s: null pointer", who);
+  PENEO_REQUIRE(bias, "%s: needs the bias tensor [B, nh, Tm, bias_ld]", who);
+  PENEO_REQUIRE(B > 0 && nh > 0 && Tm > 0 && rows > 0 && rows <= 0x7fffffff, "%s: bad sizes B=%d nh=%d Tm=%d rows=%lld", who, B, nh, Tm,
+                (long long)rows);
+  PENEO_REQUIRE(ld_qk >= (int64_t)nh * d && ld_out >= (int64_t)nh * d, "%s: leading dims too small", who);
+  PENEO_REQUIRE((int64_t)((Tm + WQ - 1) / WQ) * nh * B <= 0x7fffffff, "%s: grid too large", who);
+  AttnParams p = {};
+  p.q = q; p.k = k; p.v = v; p.ld = ld_qk; p.B = B; p.nh = nh; p.T = Tm; p.d = d; p.Tp = peneo_attn_padded_len(Tm);
+  p.scale = scale; p.bias = bias; p.bias_ld = bias_ld; p.out = out; p.ld_out = ld_out; p.lse = lse; p.keep_scale = 1.0f;
+  p.lens = lens; p.cu_rows = cu_rows; p.rows = (int)rows;
+  PENEO_REQUIRE(pipe_operands_ok(p),
+                "%s: operands must be 16-byte aligned with row strides of whole 16 bytes, and bias_ld=%lld >= Tm=%d rounded up to 32", who,
+                (long long)bias_ld, Tm);
+  return launch_attn_fwd_pipe(p, (hipStream_t)stream);
+}
+

@@ -117,6 +117,42 @@ extern "C" int peneo_encoder_layer_fwd(const peneo_encoder_layer* L, void* out, 
   return PENEO_OK;
 }
 
+// Packed inference forward (version 113): the chain above at M = rows live rows, the attention per document length
+extern "C" int peneo_encoder_layer_fwd_packed(const peneo_encoder_layer* L, const int32_t* lens, const int32_t* cu_rows, int rows, void* out,
+                                              void* workspace, size_t workspace_bytes, peneo_stream_t stream) {
+  const char* const who = "peneo_encoder_layer_fwd_packed";
+  PENEO_REQUIRE(layer_ok(L) && out && lens && cu_rows, "%s: incomplete layer description", who);
+  PENEO_REQUIRE(L->p_hidden == 0.f && L->p_attn == 0.f, "%s: inference only, dropout must be off", who);
+  PENEO_REQUIRE(L->zi == nullptr, "%s: inference only, zi (the GELU pre-activation a backward needs) must be NULL", who);
+  PENEO_REQUIRE(L->bias && !L->key_bias, "%s: needs the bias tensor [B, nh, T, bias_ld] and no key_bias", who);
+  PENEO_REQUIRE(rows > 0 && (int64_t)rows <= (int64_t)L->B * L->T, "%s: rows=%d outside 1 .. B * T = %lld", who, rows,
+                (long long)L->B * L->T);
+  PENEO_REQUIRE(workspace_bytes >= peneo_encoder_layer_workspace_bytes(rows, L->H, L->I, 0) && (workspace || workspace_bytes == 0),
+                "%s: workspace too small", who);
+  hipStream_t st = (hipStream_t)stream;
+  const int R = rows, H = L->H, I = L->I, d = H / L->nh;
+  PENEO_REQUIRE(peneo_attn_fwd_varlen_supported(PENEO_BF16, d), "%s: head dim %d has no per-document-length attention (64 only)", who, d);
+  const Ws ws{workspace, workspace_bytes};
+  const char* qkv = reinterpret_cast<const char*>(L->qkv);
+  peneo_gemm_epilogue ep = {};
+  ep.bias = L->bqkv;
+  STAGE_TRY(gemm(1, 1, R, 3 * H, H, L->x, H, L->Wqkv, H, L->qkv, 3 * H, PENEO_BF16, ep, ws, st));
+  STAGE_TRY(peneo_attn_fwd_varlen(PENEO_BF16, qkv, qkv + 2 * (size_t)H, qkv + 4 * (size_t)H, 3 * H, R, lens, cu_rows, L->B, L->nh, L->T, d,
+                                  L->attn_scale, L->bias, L->bias_ld, L->att, H, L->lse, st));
+  ep = {};
+  ep.bias = L->bo; ep.residual = L->x; ep.ld_res = H;
+  STAGE_TRY(gemm(1, 1, R, H, H, L->att, H, L->Wo, H, L->h1, H, PENEO_BF16, ep, ws, st));
+  STAGE_TRY(peneo_layernorm_fwd(PENEO_BF16, L->h1, 0, 0, L->a, 0, 0, L->g1, L->b1, L->eps, L->m1, L->r1, R, H, 0.f, 0u, st));
+  ep = {};
+  ep.bias = L->bi; ep.act = PENEO_ACT_GELU;
+  STAGE_TRY(gemm(1, 1, R, I, H, L->a, H, L->Wi, H, L->inter, I, PENEO_BF16, ep, ws, st));
+  ep = {};
+  ep.bias = L->bo2; ep.residual = L->a; ep.ld_res = H;
+  STAGE_TRY(gemm(1, 1, R, H, I, L->inter, I, L->Wo2, I, L->h2, H, PENEO_BF16, ep, ws, st));
+  STAGE_TRY(peneo_layernorm_fwd(PENEO_BF16, L->h2, 0, 0, out, 0, 0, L->g2, L->b2, L->eps, L->m2, L->r2, R, H, 0.f, 0u, st));
+  return PENEO_OK;
+}
+
 extern "C" int peneo_encoder_layer_mxfp8_supported(int rows, int H, int I) {
   return rows > 0 && H > 0 && I > 0 && H <= 0x7fffffff / 3 && peneo_gemm_mxfp8_supported(rows, 3 * H, H) && peneo_gemm_mxfp8_supported(rows, H, H) &&
          peneo_gemm_mxfp8_supported(rows, I, H) && peneo_gemm_mxfp8_supported(rows, H, I);

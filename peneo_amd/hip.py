@@ -133,6 +133,9 @@ SIGNATURES = {
     "peneo_visual_assemble_bwd": (_i, [_i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "peneo_relpos_inputs": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "peneo_relpos_buckets": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "peneo_pack_plan": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "peneo_rows_pack": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i64, _vp, _i64, _vp]),
+    "peneo_rows_unpack": (_i, [_vp, _i64, _vp, _vp, _vp, _i, _i, _i64, _vp, _vp]),
     "peneo_relpos_bias_fwd": (_i, [_i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _f, _i, _i, _i, _i, _vp, _vp, _vp]),
     "peneo_relpos_bias_bwd_layers": (_i, [_vp, _i, _i64, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _f, _i, _i, _i, _i, _vp]),
     "peneo_relpos_bias_bwd": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _f, _i, _i, _i, _vp]),
@@ -140,6 +143,8 @@ SIGNATURES = {
     "peneo_attn_padded_dim": (_i, [_i]),
     "peneo_head_transpose": (_i, [_i, _vp, _i64, _i, _i, _i, _i, _vp, _vp]),
     "peneo_attn_fwd": (_i, [_i, _vp, _vp, _vp, _i64, _vp, _i, _i, _i, _i, _f, _vp, _i64, _vp, _vp, _i64, _vp, _f, _vp, _vp]),
+    "peneo_attn_fwd_varlen_supported": (_i, [_i, _i]),
+    "peneo_attn_fwd_varlen": (_i, [_i, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _i, _i, _i, _i, _f, _vp, _i64, _vp, _i64, _vp, _vp]),
     "peneo_attn_drop_words_dims": (None, [_i, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "peneo_attn_drop_words_count": (_i64, [_i, _i, _i]),
     "peneo_attn_drop_words": (_i, [_vp, _i, _i, _i, _f, _u32, _vp]),
@@ -211,6 +216,7 @@ SIGNATURES = {
     "peneo_struct_bytes": (C.c_size_t, [_i]),
     "peneo_encoder_layer_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i]),
     "peneo_encoder_layer_fwd": (_i, [_vp, _vp, _vp, C.c_size_t, _vp]),
+    "peneo_encoder_layer_fwd_packed": (_i, [_vp, _vp, _vp, _i, _vp, _vp, C.c_size_t, _vp]),
     "peneo_encoder_layer_mxfp8_supported": (_i, [_i, _i, _i]),
     "peneo_encoder_layer_fwd_mxfp8": (_i, [_vp, _vp, _vp, _vp]),
     "peneo_encoder_layer_bwd": (_i, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp]),

@@ -129,6 +129,8 @@ class _FwdState:
         self.grad_pools = None  # [layers, pool] fp32 accumulators of the layer stages' backward (one zero fill per step)
         self.grad_mode = False  # torch.is_grad_enabled() of the model call (inside an autograd.Function it is always off)
         self.fill_event = None  # the side-stream zero fill of the embedding stage's gradient buffer (main-pool memory)
+        self.packed = False    # encoder_route said "packed": the embedding stage leaves K4 to LayoutLMv3Model._packed_layers ...
+        self.rel = None        # ... and hands it (pos, xs, ys, lut1, lut2, w1, wx, wy) here
 
 
 # ------------------------------------------------------------------------------------------------
@@ -194,7 +196,15 @@ class _EmbedStage(torch.autograd.Function):
         st.key_mask = km
 
         # K4: bucket maps + summed bias, shared by every layer
-        if use1 or use2:
+        if st.packed:
+            # packed inference (encoder_route: there is a bias tensor): the maps and the bias are built for the packed tokens, at
+            # [B, nh, Tm, Tp(Tm)], once the lengths are known
+            ri = iter(rel)
+            st.rel = (pos_t, xs, ys,
+                      model.lut("1d", cfg.rel_pos_bins, cfg.max_rel_pos, dev) if use1 else None,
+                      model.lut("2d", cfg.rel_2d_pos_bins, cfg.max_rel_2d_pos, dev) if use2 else None,
+                      next(ri) if use1 else None, next(ri) if use2 else None, next(ri) if use2 else None)
+        elif use1 or use2:
             lut1 = model.lut("1d", cfg.rel_pos_bins, cfg.max_rel_pos, dev) if use1 else None
             lut2 = model.lut("2d", cfg.rel_2d_pos_bins, cfg.max_rel_2d_pos, dev) if use2 else None
             st.buckets = ops.relpos_buckets(pos_t, xs, ys, B, T, lut1, cfg.rel_pos_bins // 2, lut2, cfg.rel_2d_pos_bins // 2)
@@ -328,10 +338,12 @@ class _LayerBuffers:
         L.r2 = L.m2 + 4 * R
 
 
-def _describe_layer(model, st, idx, params, x, bufs):
+def _describe_layer(model, st, idx, params, x, bufs, T_packed=None):
     (wq, bq, wk, bk, wv, bv, wo, bo, g1, b1, wi, bi, wo2, bo2, g2, b2) = params
     cfg, wc, dt = model.config, model.weight_cache, st.dtype
     B, S, T = st.dims
+    if T_packed is not None:       # the packed forward: T is Tm, the extent of st.bias and of the lse buffer
+        T = T_packed
     H, nh = cfg.hidden_size, cfg.num_attention_heads
     seeds = st.seeds
     site = 16 * (idx + 1)
@@ -703,6 +715,20 @@ def layer_params(layer: LayoutLMv3Layer) -> List[torch.Tensor]:
 
 
 # ------------------------------------------------------------------------------------------------
+# packed ("varlen") inference: which forwards skip the padded text tokens
+# ------------------------------------------------------------------------------------------------
+def encoder_route(*, switch: bool, grad_enabled: bool, training: bool, dtype: torch.dtype, has_mask: bool, stage_calls: bool,
+                  head_dim: int, has_bias: bool, encoder_format: str) -> str:
+    """"packed" or "padded": the route of one backbone forward, decided once from host-side facts (no GPU).  "packed" needs ALL of:
+    set_skip_padded_tokens on, no autograd (torch.is_grad_enabled() false), eval mode, bf16 compute, an attention_mask, the composite
+    stage calls on (PENEO_STAGE_CALLS), head dim 64 (ops.attn_fwd_varlen_supported), a relative-position bias tensor, and the encoder
+    format "bf16".  Every other forward is "padded": today's path, unchanged in every bit."""
+    packed = (bool(switch) and not grad_enabled and not training and dtype == torch.bfloat16 and bool(has_mask) and bool(stage_calls)
+              and head_dim == 64 and bool(has_bias) and encoder_format == "bf16" and ops.attn_fwd_varlen_supported(dtype, head_dim))
+    return "packed" if packed else "padded"
+
+
+# ------------------------------------------------------------------------------------------------
 # the backbone module
 # ------------------------------------------------------------------------------------------------
 class LayoutLMv3Model(nn.Module):
@@ -729,6 +755,7 @@ class LayoutLMv3Model(nn.Module):
         self.weight_cache = WeightCache()
         self.compute_dtype = torch.float32
         self.encoder_format = "bf16"      # set_encoder_format
+        self.skip_padded_tokens = os.environ.get("PENEO_SKIP_PADDED_TOKENS", "0") == "1"   # set_skip_padded_tokens
         self.wgrad_on_side_stream = os.environ.get("PENEO_WGRAD_STREAM", "1") != "0"
         self.defer_wgrad_join = os.environ.get("PENEO_DEFER_JOIN", "1") != "0"
         self._luts = {}
@@ -742,6 +769,8 @@ class LayoutLMv3Model(nn.Module):
         if fmt not in ("bf16", "mxfp8"):
             raise ValueError(f"unknown encoder format {fmt!r} (expected 'bf16' or 'mxfp8')")
         if fmt == "mxfp8":
+            if self.skip_padded_tokens:
+                raise ValueError("mxfp8 encoder layers do not combine with set_skip_padded_tokens(True): the packed forward is bf16")
             if self.compute_dtype != torch.bfloat16:
                 raise ValueError("mxfp8 encoder layers need compute dtype torch.bfloat16")
             H, I = self.config.hidden_size, self.config.intermediate_size
@@ -749,6 +778,49 @@ class LayoutLMv3Model(nn.Module):
                 raise ValueError(f"mxfp8 encoder layers do not support H = {H}, I = {I} (peneo_gemm_mxfp8 needs K % 128 == 0, N % 32 == 0)")
         self.encoder_format = fmt
         return self
+
+    def set_skip_padded_tokens(self, on: bool) -> "LayoutLMv3Model":
+        """Opt-in inference switch (default off; PENEO_SKIP_PADDED_TOKENS=1 turns it on at construction).  On: a forward that
+        encoder_route calls "packed" - no autograd, eval mode, bf16 compute, an attention_mask, head dim 64, a relative-position bias -
+        packs the live tokens (mask = 1 text tokens and all visual tokens; holes in the mask allowed) to contiguous rows after the
+        embedding stage, runs the encoder layers on those R = sum T_b rows with a per-document-length attention
+        (peneo_encoder_layer_fwd_packed) and scatters the result back to [B, T, H].  The rows of masked tokens in the returned hidden
+        state are ZEROS (the default path returns what the layers make of the padding embeddings), so whatever reads those rows -
+        the logits and all-pairs losses of pairs that touch padding - differs from the default path; set_skip_padded_pairs(True) on
+        the decoder beside this switch keeps such pairs out of maps and losses.  The packed forward makes ONE device-to-host read
+        (the B document lengths) after the embedding stage: it synchronises the host with the stream there.  Every other forward is
+        today's path in every bit.  Not together with set_encoder_format("mxfp8"): ValueError."""
+        if on and self.encoder_format == "mxfp8":
+            raise ValueError("set_skip_padded_tokens(True) does not combine with set_encoder_format('mxfp8'): the packed forward is bf16")
+        self.skip_padded_tokens = bool(on)
+        return self
+
+    def _packed_layers(self, st, emb: torch.Tensor) -> torch.Tensor:
+        """The encoder layers of a "packed" forward: emb [B * T, H] from the embedding stage -> hidden [B, T, H] with zero rows for
+        the masked tokens.  One host read (lens); every buffer of the layers is allocated once and reused by all of them."""
+        cfg, dt = self.config, st.dtype
+        B, S, T = st.dims
+        H, nh, I = cfg.hidden_size, cfg.num_attention_heads, cfg.intermediate_size
+        dev = emb.device
+        lens, cu_rows, live_t = ops.pack_plan(st.key_mask)
+        lens_host = lens.tolist()                     # the one device-to-host read of the packed forward (B int32)
+        R, Tm = sum(lens_host), max(lens_host)
+        pos_t, xs, ys, lut1, lut2, w1, wx, wy = st.rel
+        per_doc = lambda t: ops.rows_pack(t, live_t, lens, None, Tm) if t is not None else None
+        bk1, bkx, bky = ops.relpos_buckets(per_doc(pos_t), per_doc(xs), per_doc(ys), B, Tm, lut1, cfg.rel_pos_bins // 2, lut2,
+                                           cfg.rel_2d_pos_bins // 2)
+        # (no key mask: a document's keys from lens[b] on are never read into the softmax by the per-document-length attention)
+        st.bias = ops.relpos_bias_fwd(dt, bk1, bkx, bky, w1, wx, wy, 1.0 / math.sqrt(H // nh), B, nh, Tm)
+        x = ops.rows_pack(emb.view(B, T, H), live_t, lens, cu_rows, Tm, rows=R)
+        bufs = _LayerBuffers(R, H, I, B * nh * Tm, False, dev)
+        wsb = _layer_ws_bytes(R, H, I, 0)
+        ws = torch.empty(wsb, dtype=torch.uint8, device=dev) if wsb else None
+        outs = [torch.empty((R, H), dtype=dt, device=dev) for _ in range(2)]
+        for i, layer in enumerate(self.encoder.layer):
+            L, keep = _describe_layer(self, st, i, layer_params(layer), x, bufs, T_packed=Tm)
+            x = ops.encoder_layer_fwd_packed(L, lens, cu_rows, R, outs[i & 1], ws)
+            del keep
+        return ops.rows_unpack(x, live_t, lens, cu_rows)
 
     def check_encoder_format(self) -> None:
         """Raises before anything runs when the MXFP8 encoder cannot serve this forward (it has no backward and reads bf16)."""
@@ -923,10 +995,17 @@ class LayoutLMv3Model(nn.Module):
         st.dtype = self.compute_dtype
         st.grad_mode = torch.is_grad_enabled()
         st.seeds = DropoutSeeds(self.training, cfg.hidden_dropout_prob, cfg.attention_probs_dropout_prob)
+        st.packed = encoder_route(
+            switch=self.skip_padded_tokens, grad_enabled=st.grad_mode, training=self.training, dtype=st.dtype,
+            has_mask=attention_mask is not None, stage_calls=_use_stage_calls(self, st, cfg.hidden_size, cfg.intermediate_size),
+            head_dim=cfg.hidden_size // cfg.num_attention_heads,
+            has_bias=cfg.has_relative_attention_bias or cfg.has_spatial_attention_bias, encoder_format=self.encoder_format) == "packed"
         x = _EmbedStage.apply(self, st, input_ids.contiguous(), bbox.contiguous(),
                               attention_mask.contiguous() if attention_mask is not None else None, image,
                               *self.embed_params())
         _, _, T = st.dims
+        if st.packed:
+            return (self._packed_layers(st, x),)
         mx = self.encoder_format == "mxfp8"
         for i, layer in enumerate(self.encoder.layer):
             x = _mx_layer_forward(self, st, i, x, layer_params(layer)) if mx else _LayerStage.apply(self, st, i, x, *layer_params(layer))

@@ -210,6 +210,21 @@ class PEneoModel(PEneoPreTrainedModel):
         self.peneo_decoder.set_skip_padded_pairs(on)
         return self
 
+    def set_skip_padded_tokens(self, on: bool) -> "PEneoModel":
+        """Opt-in inference switch of the LayoutLMv3 backbone (default off; PENEO_SKIP_PADDED_TOKENS=1 turns it on at construction;
+        LayoutLMv3Model.set_skip_padded_tokens): eval forwards without gradients, at bf16 compute and with an ``attention_mask``, run
+        the encoder layers over the live tokens only (mask = 1 text tokens plus all visual tokens), with one device-to-host read of the
+        B document lengths per forward.  The hidden-state rows of masked tokens are then zeros, so the logits of pairs that touch
+        padding, and with them the returned all-pairs losses, differ from the default path's: use set_skip_padded_pairs(True) beside
+        this switch (the two are independent; the MXFP8 pair heads combine with this one).  Every other forward is unchanged.  A LiLT
+        backbone, and set_encoder_format("mxfp8") together with the switch, raise ValueError."""
+        if not hasattr(self.backbone, "set_skip_padded_tokens"):
+            if on:
+                raise ValueError("set_skip_padded_tokens exists for the LayoutLMv3 backbone only, not for LiLT")
+            return self
+        self.backbone.set_skip_padded_tokens(on)
+        return self
+
     def set_encoder_format(self, fmt: str) -> "PEneoModel":
         """"bf16" (default) or "mxfp8": the MXFP8 inference path of the backbone's encoder layers (LayoutLMv3Model.set_encoder_format;
         eval forwards without gradients only).  Independent of set_pair_heads_format.  "mxfp8" needs compute dtype torch.bfloat16 and

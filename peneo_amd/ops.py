@@ -662,6 +662,145 @@ def attn_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, B: int, nh: int,
     return out, lse
 
 
+# ----------------------------------------------------------------------------------------------
+# packed ("varlen") inference: the plan, the row movers, the per-document-length attention (include/peneo_hip.h, version 113)
+# ----------------------------------------------------------------------------------------------
+def _check_plan(who: str, dev, B: int, lens: torch.Tensor, cu_rows: Optional[torch.Tensor], live_t: Optional[torch.Tensor] = None,
+                T: Optional[int] = None) -> None:
+    def bad(t, shape):
+        return (not torch.is_tensor(t)) or t.dtype != torch.int32 or t.device != dev or tuple(t.shape) != shape or not t.is_contiguous()
+    if bad(lens, (B,)):
+        raise hip.PeneoHipError(f"{who}: lens must be a contiguous int32 [{B}] tensor on {dev}")
+    if cu_rows is not None and bad(cu_rows, (B + 1,)):
+        raise hip.PeneoHipError(f"{who}: cu_rows must be a contiguous int32 [{B + 1}] tensor on {dev}")
+    if live_t is not None and bad(live_t, (B, T)):
+        raise hip.PeneoHipError(f"{who}: live_t must be a contiguous int32 [{B}, {T}] tensor on {dev}")
+
+
+def pack_plan(key_mask: torch.Tensor):
+    """key_mask int32 [B, T] on the device (relpos_inputs' first output; holes allowed) -> (lens [B], cu_rows [B + 1], live_t [B, T]),
+    all int32: the number of live tokens per document, their exclusive prefix sum, and the position of the i-th live token of each
+    document (-1 from lens[b] on).  One launch, no host synchronisation."""
+    if not torch.is_tensor(key_mask) or key_mask.dim() != 2 or key_mask.dtype != torch.int32 or not key_mask.is_cuda \
+            or not key_mask.is_contiguous():
+        raise hip.PeneoHipError("pack_plan: key_mask must be a contiguous int32 [B, T] device tensor")
+    B, T = key_mask.shape
+    dev = key_mask.device
+    lens = torch.empty(B, dtype=torch.int32, device=dev)
+    cu_rows = torch.empty(B + 1, dtype=torch.int32, device=dev)
+    live_t = torch.empty((B, T), dtype=torch.int32, device=dev)
+    check(lib().peneo_pack_plan(ptr(key_mask), B, T, ptr(lens), ptr(cu_rows), ptr(live_t), stream()), "peneo_pack_plan")
+    return lens, cu_rows, live_t
+
+
+def _row_bytes(who: str, t: torch.Tensor, lead: int) -> int:
+    if not t.is_contiguous() or not t.is_cuda:
+        raise hip.PeneoHipError(f"{who}: tensors must be contiguous and on the device")
+    n = t.numel() // max(lead, 1) * t.element_size()
+    if n <= 0 or n % 4:
+        raise hip.PeneoHipError(f"{who}: rows of {n} bytes (a positive multiple of 4 is needed)")
+    return n
+
+
+def rows_pack(src: torch.Tensor, live_t: torch.Tensor, lens: torch.Tensor, cu_rows: Optional[torch.Tensor], Tm: int,
+              rows: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Gather the live rows of src [B, T, ...] (peneo_rows_pack).  cu_rows given: -> [rows, ...], row cu_rows[b] + i = src[b, live_t[b, i]]
+    (`rows` = cu_rows[B], known to the caller; rows of `out` that belong to no live token are left as they are).  cu_rows None: the
+    per-document layout [B, Tm, ...] with zeros from lens[b] on."""
+    if src.dim() < 2:
+        raise hip.PeneoHipError("rows_pack: src must be [B, T, ...]")
+    B, T = src.shape[:2]
+    Tm = int(Tm)
+    _check_plan("rows_pack", src.device, B, lens, cu_rows, live_t, T)
+    if not 1 <= Tm <= T:
+        raise hip.PeneoHipError(f"rows_pack: Tm = {Tm} outside 1 .. T = {T}")
+    rb = _row_bytes("rows_pack", src, B * T)
+    if cu_rows is not None:
+        if out is None:
+            if rows is None or not 1 <= int(rows) <= B * T:
+                raise hip.PeneoHipError(f"rows_pack: the cu_rows layout needs rows in 1 .. B * T = {B * T}, got {rows}")
+            out = torch.empty((int(rows),) + tuple(src.shape[2:]), dtype=src.dtype, device=src.device)
+        n_out = out.shape[0]
+    else:
+        if out is None:
+            out = torch.empty((B, Tm) + tuple(src.shape[2:]), dtype=src.dtype, device=src.device)
+        if tuple(out.shape[:2]) != (B, Tm):
+            raise hip.PeneoHipError(f"rows_pack: out must be [{B}, {Tm}, ...], got {tuple(out.shape)}")
+        n_out = B * Tm
+    if out.dtype != src.dtype or out.device != src.device or _row_bytes("rows_pack", out, n_out) != rb:
+        raise hip.PeneoHipError("rows_pack: out must have src's dtype, device and row size")
+    check(lib().peneo_rows_pack(ptr(src), ptr(live_t), ptr(lens), ptr(cu_rows), B, T, Tm, rb, ptr(out), n_out, stream()), "peneo_rows_pack")
+    return out
+
+
+def rows_unpack(src: torch.Tensor, live_t: torch.Tensor, lens: torch.Tensor, cu_rows: torch.Tensor,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Inverse of rows_pack's cu_rows layout (peneo_rows_unpack): src [rows, ...] -> [B, T, ...] with EVERY row written - row
+    (b, live_t[b, i]) from src row cu_rows[b] + i, all other rows zeros."""
+    B, T = live_t.shape
+    _check_plan("rows_unpack", src.device, B, lens, cu_rows, live_t, T)
+    if src.dim() < 1 or src.shape[0] < 1:
+        raise hip.PeneoHipError("rows_unpack: src must be [rows, ...] with rows >= 1")
+    rb = _row_bytes("rows_unpack", src, src.shape[0])
+    if out is None:
+        out = torch.empty((B, T) + tuple(src.shape[1:]), dtype=src.dtype, device=src.device)
+    if tuple(out.shape[:2]) != (B, T) or out.dtype != src.dtype or out.device != src.device or _row_bytes("rows_unpack", out, B * T) != rb:
+        raise hip.PeneoHipError(f"rows_unpack: out must be [{B}, {T}, ...] with src's dtype, device and row size")
+    check(lib().peneo_rows_unpack(ptr(src), src.shape[0], ptr(live_t), ptr(lens), ptr(cu_rows), B, T, rb, ptr(out), stream()),
+          "peneo_rows_unpack")
+    return out
+
+
+def attn_fwd_varlen_supported(dtype, d: int) -> bool:
+    """True for (torch.bfloat16, 64), the one shape attn_fwd_varlen has a kernel for (host-side, no GPU call)."""
+    code = dtype_code(dtype) if isinstance(dtype, torch.dtype) else int(dtype)
+    return bool(lib().peneo_attn_fwd_varlen_supported(code, int(d)))
+
+
+def attn_fwd_varlen(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, lens: torch.Tensor, cu_rows: torch.Tensor, nh: int, Tm: int,
+                    d: int, scale: float, bias: torch.Tensor, out: Optional[torch.Tensor] = None,
+                    lse: Optional[torch.Tensor] = None):
+    """Per-document-length attention forward (peneo_attn_fwd_varlen).  q/k/v: 2-D views [rows, nh*d] with a common row stride; the
+    rows of document b are cu_rows[b] .. + min(lens[b], Tm); bias [B, nh, Tm, bias_ld] bf16.  out [rows, nh*d] / lse [B, nh, Tm] may
+    be given; rows past a document's length in lse, and rows of out that belong to no document, are not written.  bf16, d = 64 only:
+    anything else raises (there is no fallback)."""
+    B = lens.shape[0] if torch.is_tensor(lens) and lens.dim() == 1 else -1
+    _check_plan("attn_fwd_varlen", q.device, B, lens, cu_rows)
+    if not (q.dim() == k.dim() == v.dim() == 2 and q.shape == k.shape == v.shape and q.stride(0) == k.stride(0) == v.stride(0)
+            and q.stride(1) == k.stride(1) == v.stride(1) == 1 and q.shape[1] == nh * d):
+        raise hip.PeneoHipError("attn_fwd_varlen: q / k / v must be [rows, nh * d] views with one row stride")
+    rows, Tm = q.shape[0], int(Tm)
+    if not torch.is_tensor(bias) or bias.dim() != 4 or tuple(bias.shape[:3]) != (B, nh, Tm) or bias.dtype != q.dtype \
+            or not bias.is_contiguous() or bias.device != q.device:
+        raise hip.PeneoHipError(f"attn_fwd_varlen: bias must be a contiguous {q.dtype} [{B}, {nh}, {Tm}, bias_ld] tensor")
+    if out is None:
+        out = torch.empty((rows, nh * d), dtype=q.dtype, device=q.device)
+    if lse is None:
+        lse = torch.empty((B, nh, Tm), dtype=torch.float32, device=q.device)
+    if tuple(out.shape) != (rows, nh * d) or out.stride(1) != 1 or out.dtype != q.dtype or tuple(lse.shape) != (B, nh, Tm) \
+            or lse.dtype != torch.float32 or not lse.is_contiguous():
+        raise hip.PeneoHipError("attn_fwd_varlen: out must be [rows, nh * d], lse a contiguous fp32 [B, nh, Tm]")
+    check(lib().peneo_attn_fwd_varlen(dtype_code(q.dtype), ptr(q), ptr(k), ptr(v), q.stride(0), rows, ptr(lens), ptr(cu_rows), B, nh, Tm,
+                                      d, scale, ptr(bias), bias.shape[-1], ptr(out), out.stride(0), ptr(lse), stream()),
+          "peneo_attn_fwd_varlen")
+    return out, lse
+
+
+def encoder_layer_fwd_packed(layer: "hip.EncoderLayer", lens: torch.Tensor, cu_rows: torch.Tensor, rows: int, out: torch.Tensor,
+                             workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One C call for the packed inference forward of an encoder layer (include/peneo_hip.h, peneo_encoder_layer_fwd_packed): `layer`
+    holds device pointers of buffers with `rows` rows that the caller keeps alive (layer.T = Tm); out [rows, H] bf16 is written."""
+    rows = int(rows)
+    _check_plan("encoder_layer_fwd_packed", out.device, int(layer.B), lens, cu_rows)
+    if out.dtype != torch.bfloat16 or not out.is_contiguous() or tuple(out.shape) != (rows, int(layer.H)):
+        raise hip.PeneoHipError(f"encoder_layer_fwd_packed: out must be a contiguous bf16 [{rows}, {int(layer.H)}] tensor")
+    wsb = workspace.numel() * workspace.element_size() if workspace is not None else 0
+    with kernel_timer("encoder_layer_fwd_packed"):
+        check(lib().peneo_encoder_layer_fwd_packed(C.byref(layer), ptr(lens), ptr(cu_rows), rows, ptr(out), ptr(workspace), wsb, stream()),
+              "peneo_encoder_layer_fwd_packed")
+    return out
+
+
 def attn2_supported(dtype: torch.dtype, d_a: int, d_b: int) -> bool:
     """Whether attn2_fwd takes this dtype and pair of head dims (peneo_attn2_supported: a host-side question, no GPU call)."""
     return bool(lib().peneo_attn2_supported(dtype_code(dtype), d_a, d_b))
