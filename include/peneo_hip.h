@@ -828,7 +828,9 @@ typedef struct peneo_encoder_layer {
   const void* bias; int64_t bias_ld; const float* key_bias; const uint32_t* drop_words;
   const void* x; void* qkv; void* att; float* lse; void* h1; float* m1; float* r1; void* a; void* zi; void* inter; void* h2;
   float* m2; float* r2;
-  int32_t B, T, H, nh, I, reserved;
+  int32_t B, T, H, nh, I;
+  int32_t wgrad_last;       /* backward only: != 0 marks the layer whose backward the caller issues last (layer 0); read under
+                             * peneo_gemm_group_set_nn384_mode(2) alone.  (The field was `reserved`: the struct's size is unchanged.) */
   float eps, attn_scale, p_hidden, p_attn;
   uint32_t seed_o, seed_o2;
 } peneo_encoder_layer;
@@ -930,19 +932,29 @@ void peneo_gemm_set_big_mode(int mode);
 int peneo_gemm_big_mode(void);            /* the mode in force (tests restore what they found) */
 /* The same for weight gradients with A = [K, M] and B = [K, N] (gemm_big.hip, 384 x 192 tiles x split_k one-per-CU workgroups whose
  * fp32 partials the split-k reduce sums in slice order).  The rule: bf16 operands, fp32 C, no epilogue option beyond accumulate,
- * no a_colsum, M % 384 == 0, N % 192 == 0, K % 64 == 0, 16-byte aligned operands, and K >= 65536 (the pair heads' dW1; every
+ * no a_colsum, M % 384 == 0, N % 192 == 0, K % 8 == 0, 16-byte aligned operands, and K >= 65536 (the pair heads' dW1; every
  * other caller keeps the 128 x 128 kernel).  0 = off, 1 = that rule (default; also set by PENEO_GEMM_NN384), 2 = the rule without
  * its bound on K (tests, tools).  PENEO_GEMM_BIG = 0 / peneo_gemm_set_big_mode(0) switches it off as well.
  * Diagnostics like the setter above (process-wide plain globals, not thread-safe, for tests, tools and the decoder's split choice):
  * peneo_gemm_nn384_mode: the mode in force (0 while big tiles are off).  peneo_gemm_nn384_launches: how many peneo_gemm calls of
  * this process took the path (the 128 x 128 kernel sums the same k-steps in the same order, so a result cannot tell which ran).
  * peneo_gemm_nn384_shape_ok: 1 if the SHAPE part of the rule holds for (M, N, K) under the mode in force - the library's one copy of
- * 384 / 192 / 64 / 65536; a call with that shape still keeps the 128 x 128 kernel when its layouts, C type, epilogue or the
+ * 384 / 192 / 8 / 65536; a call with that shape still keeps the 128 x 128 kernel when its layouts, C type, epilogue or the
  * alignment of an operand (16-byte bases, lda % 8, ldb % 8, ldc % 4, 64 rows of A or B below 2 GiB) are outside the rule. */
 void peneo_gemm_set_nn384_mode(int mode);
 int peneo_gemm_nn384_mode(void);
 uint64_t peneo_gemm_nn384_launches(void);
 int peneo_gemm_nn384_shape_ok(int M, int N, int K);
+/* The same tile for peneo_gemm_group: ONE launch walks the 384 x 192 tiles of all problems of the call, each workgroup the whole K of
+ * its tile (no split, no workspace, no atomics: the same bits on every run, and the bits of the 128 x 128 group).  Taken when EVERY
+ * problem passes: bf16 operands, a_kmajor == b_kmajor == 0, fp32 C, no epilogue option beyond accumulate, M % 384 == 0, N % 192 == 0,
+ * K % 8 == 0 (a ragged last k-tile requests only the rows below K), 16-byte aligned A / B / C bases, lda % 8, ldb % 8, ldc % 4, 64 rows
+ * of A or B below 2 GiB; otherwise the whole call keeps the 128 x 128 kernel.  Mode: 0 = off, 1 = on (default), 2 = on except in the
+ * peneo_encoder_layer_bwd call whose layer has wgrad_last != 0; also set by PENEO_WGRAD_NN384; off while big tiles are off.
+ * peneo_gemm_group_nn384_launches: how many peneo_gemm_group calls of this process took the path. */
+void peneo_gemm_group_set_nn384_mode(int mode);
+int peneo_gemm_group_nn384_mode(void);
+uint64_t peneo_gemm_group_nn384_launches(void);
 /* The same for the persistent launch (gemm_sk.hip; first choice of peneo_gemm for large bf16 problems with k-major A and B):
  * 0 = off (the tiled kernels above), 1 = the measured rules (default; also set by PENEO_GEMM_SK), F * 1000 + BN = force ranges of
  * whole 32 F x BN tiles, + 100000 = force ranges that cut tiles (stream-k), wherever the kernel's constraints hold (B k-major among

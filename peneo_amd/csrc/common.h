@@ -31,6 +31,12 @@ int order_dependent(const char* entry_point);
     if (od_rc_ != PENEO_OK) return od_rc_;                        \
   } while (0)
 
+// peneo_gemm_group with one more word from the caller (gemm.hip): allow_nn384 = false keeps the 128 x 128 group whatever
+// PENEO_WGRAD_NN384 says.  gemm_group_nn384_mode (gemm_big.hip): that mode, 0 / 1 / 2 (peneo_gemm_group_set_nn384_mode).
+int gemm_group_launch(int dtype, int a_kmajor, int b_kmajor, int c_dtype, const peneo_gemm_problem* problems, int n,
+                      peneo_stream_t stream, bool allow_nn384);
+int gemm_group_nn384_mode();
+
 // A kernel may use more dynamic LDS than the default only once that is set for it.  raise_dynamic_lds sets it, on every call
 // (allow_dynamic_lds in gemm_common.h is the once-per-device form), and returns PENEO_OK or, with the one spelling of the error
 // (dynamic_lds_error), PENEO_ERR_LAUNCH.

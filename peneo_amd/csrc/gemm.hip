@@ -789,7 +789,6 @@ __global__ __launch_bounds__(256, 2) void gemm_dma_pipe_kernel(GemmParams p) {
 // Several independent GEMMs of one operand layout in ONE launch (no split-k): the tiles of all problems are numbered
 // consecutively, the XCD-aware order runs over the whole launch.  Used for the four weight gradients of an encoder layer:
 // 432 tiles with the full K = tokens each, instead of four split-k launches of ~450 short workgroups plus four reductions.
-constexpr int GEMM_GROUP_MAX = 4;
 struct GemmGroup {
   GemmParams p[GEMM_GROUP_MAX];
   int first_tile[GEMM_GROUP_MAX + 1];
@@ -898,6 +897,12 @@ extern "C" size_t peneo_gemm_workspace_bytes(int M, int N, int K, int split_k) {
 
 extern "C" int peneo_gemm_group(int dtype, int a_kmajor, int b_kmajor, int c_dtype, const peneo_gemm_problem* problems, int n,
                                 peneo_stream_t stream) {
+  return gemm_group_launch(dtype, a_kmajor, b_kmajor, c_dtype, problems, n, stream, true);
+}
+
+// allow_nn384 = false: the caller keeps the 128 x 128 group whatever the mode says (peneo_encoder_layer_bwd under mode 2, last layer)
+int peneo::gemm_group_launch(int dtype, int a_kmajor, int b_kmajor, int c_dtype, const peneo_gemm_problem* problems, int n,
+                             peneo_stream_t stream, bool allow_nn384) {
   PENEO_REQUIRE(dtype == PENEO_BF16, "peneo_gemm_group: bf16 operands only");
   PENEO_REQUIRE(c_dtype == PENEO_F32 || c_dtype == PENEO_BF16, "peneo_gemm_group: bad c_dtype %d", c_dtype);
   PENEO_REQUIRE(problems && n >= 1 && n <= GEMM_GROUP_MAX, "peneo_gemm_group: 1..%d problems (got %d)", GEMM_GROUP_MAX, n);
@@ -941,6 +946,11 @@ extern "C" int peneo_gemm_group(int dtype, int a_kmajor, int b_kmajor, int c_dty
   const int shmem = 2 * 2 * TILE_BYTES;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const bool ak = a_kmajor != 0, bk = b_kmajor != 0;
+  // weight gradients whose outputs are whole 384 x 192 tiles: 96 one-per-CU workgroups in place of 432 (gemm_big.hip holds the rule)
+  if (allow_nn384 && !ak && !bk && c_dtype == PENEO_F32) {
+    const int big = launch_gemm_big_group(g.p, n, st);
+    if (big != 0) return big < 0 ? big : PENEO_OK;
+  }
 #define PENEO_GROUP_LAUNCH(AK_, BK_)                                                                                         \
   {                                                                                                                          \
     static std::atomic<uint64_t> lds_devices{0};                                                                             \

@@ -8,7 +8,8 @@
 // N = 2304, 240 tiles of 384 x 192 for N = 3072, 138 tiles of 256 x 128 for N = 768).
 //
 // Layouts: A k-major [M][K]; B k-major [N][K] (forward, x W^T) or mn-major [K][N] (dgrad, dy W).  K % 64 == 0.
-// Both mn-major (A [K][M], B [K][N]: a weight gradient dy^T x) on the 384 x 192 tile, with split-k: launch_gemm_big_nn below.
+// Both mn-major (A [K][M], B [K][N]: a weight gradient dy^T x) on the 384 x 192 tile, with split-k: launch_gemm_big_nn below;
+// that form alone takes K % 8 == 0 (a ragged last k-tile, see "tail" in the body) and has a grouped launch (launch_gemm_big_group).
 // LDS image of a k-major tile: rows of 128 B (64 k), 16-byte slot s of row r at slot s ^ ((r >> 1) & 7) (swizzle applied
 // to the SOURCE address of each LDS-DMA lane, destination lane-linear: 1 KiB piece = 8 rows); fragments by ds_read_b128.
 // mn-major tile: 1 KiB pieces of [8 k][64 columns], the two 64-byte halves of a line swapped when (k >> 1) & 1; fragments
@@ -21,6 +22,7 @@
 #include <type_traits>
 #include "common.h"
 #include "gemm_common.h"
+#include "gemm_walk.h"
 
 namespace peneo {
 
@@ -41,31 +43,36 @@ struct BigCfg {
   static_assert(LDS_BYTES <= 160 * 1024, "LDS");
 };
 
-// PART: the launch is tiles x split_k workgroups, workgroup (tile, z) multiplies k-tiles [z kt_per_split, (z + 1) kt_per_split) and
-// leaves its tile as plain fp32 in slice z of p.ws (peneo_gemm's split-k reduce runs the caller's epilogue).  Its own
-// instantiation: the fused epilogue is not part of its code.
-template <typename C, bool PART = false>
-__global__ __launch_bounds__(512) void gemm_big_kernel(GemmParams p, int tiles_n) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
+// One problem of a grouped launch (launch_gemm_big_group): what the body reads of a problem, and nothing of the fused epilogue
+struct BigGroupProblem {
+  const void* A; const void* B; void* C;
+  int64_t lda, ldb, ldc;
+  int M, N, K, accumulate;
+};
+struct BigGroup {
+  BigGroupProblem q[GEMM_GROUP_MAX];
+  int first_tile[GEMM_GROUP_MAX + 1];
+  int tiles_n[GEMM_GROUP_MAX];
+  int n;
+};
+
+// How a workgroup leaves its tile:
+//   EP_FUSED  the shared fused epilogue of peneo_gemm (gemm_common.h)
+//   EP_PART   plain fp32 in slice zsplit of p.ws: the launch is tiles x split_k workgroups, workgroup (tile, z) multiplies k-tiles
+//             [z kt_per_split, (z + 1) kt_per_split) and peneo_gemm's split-k reduce runs the caller's epilogue
+//   EP_GROUP  fp32 C (+= with `accumulate`), the only epilogue a grouped problem on this tile may ask for
+// Each is its own instantiation: the fused epilogue is part of the first one's code only.
+enum { EP_FUSED = 0, EP_PART = 1, EP_GROUP = 2 };
+
+// The workgroup's tile (m0, n0) over k-tiles [kt0, kt0 + ktiles) of 64, all of them full, and then, where tail_pieces > 0, the
+// ragged last k-tile of 8 * tail_pieces rows (mn-major operands only; the caller passes 0 everywhere else).
+template <typename C, int EPI, typename P>
+__device__ __forceinline__ void gemm_big_body(const P& p, char* smem, const int m0, const int n0, const int zsplit, const int kt0,
+                                              const int ktiles, const int tail_pieces) {
   constexpr int FM = C::FM, FN = C::FN, NSTAGE = C::NSTAGE;
   const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / C::WGN, wn = wave % C::WGN;
-
-  // XCD-aware tile order: workgroup ids go round-robin to the 8 XCDs; every XCD gets a contiguous band of tiles, n fastest
-  const int total = gridDim.x, lin = blockIdx.x;
-  const int q8 = total >> 3, r8 = total & 7, xcd = lin & 7, slot = lin >> 3;
-  int tile = xcd * q8 + min(xcd, r8) + slot;
-  // (PART: the order above runs over the whole launch, slice-major: the tiles of one k-range are neighbours on an XCD)
-  int zsplit = 0, kt0 = 0, ktiles = p.K / 64;
-  if constexpr (PART) {
-    const int tiles = total / p.split_k;
-    zsplit = tile / tiles;
-    tile -= zsplit * tiles;
-    kt0 = zsplit * p.kt_per_split;
-    ktiles = min(ktiles, kt0 + p.kt_per_split) - kt0;
-  }
-  const int m0 = (tile / tiles_n) * C::BM, n0 = (tile % tiles_n) * C::BN;
 
   const bf16_t* A = reinterpret_cast<const bf16_t*>(p.A);
   const bf16_t* B = reinterpret_cast<const bf16_t*>(p.B);
@@ -237,6 +244,43 @@ __global__ __launch_bounds__(512) void gemm_big_kernel(GemmParams p, int tiles_n
     if (more) issue_group(std::integral_constant<int, 3>{});
     mma(fa1, fb1);
   }
+  // ---- tail (A [K][M], B [K][N], K % 64 != 0): the last k-tile has tail_pieces < 8 row blocks of 8 k.  Decided once per
+  //      workgroup, behind the loop over full tiles, whose code it does not touch.  A piece whose row block lies at or beyond K
+  //      is NOT requested (no address of such a row is formed, clamped or not): its 1 KiB of LDS is zeroed with ds stores
+  //      instead, and all four k-steps run, as the 128 x 128 kernel runs them over its zero lines (the same sums in the same order).
+  //      Which wait proves what:
+  //        barrier 1    every wave has read its last fragments of the full tiles: stage 0 may be overwritten;
+  //        vmcnt(0)     this wave's requested pieces have landed.  The count needs no PPW bookkeeping: the loop's last iteration
+  //                     waited for vmcnt(0) and issued nothing (`more` is false there; the two-stage ring waits for 0 in every
+  //                     iteration), so the tail's own requests are the only ones outstanding, however many this wave has;
+  //        barrier 2    __syncthreads waits for this wave's ds stores (lgkmcnt) and then for every wave: all pieces and all
+  //                     zeros of the stage are visible before the first fragment read. ----
+  if constexpr (!C::AK && !C::BK) {
+    static_assert(C::AK || C::BK || NSTAGE == 2, "the tail's vmcnt(0) argument above is the two-stage ring's");
+    if (tail_pieces > 0) {
+      __syncthreads();
+      dbase = __builtin_amdgcn_readfirstlane(lds0 + wave * 1024);
+      const uint4 zero4 = make_uint4(0u, 0u, 0u, 0u);
+#pragma unroll
+      for (int u = 0; u < C::APW; ++u) {
+        if (walk_piece_in_tail(wave + 8 * u, C::BM / 64, tail_pieces)) lds_dma_1k_s<0>(offA[u], bA, dbase + u * 8192);
+        else *reinterpret_cast<uint4*>(smem + (wave + 8 * u) * 1024 + lane * 16) = zero4;
+      }
+#pragma unroll
+      for (int u = 0; u < C::BPW; ++u) {
+        if (walk_piece_in_tail(wave + 8 * u, C::BN / 64, tail_pieces)) lds_dma_1k_s<0>(offB[u], bB, dbase + C::A_BYTES + u * 8192);
+        else *reinterpret_cast<uint4*>(smem + C::A_BYTES + (wave + 8 * u) * 1024 + lane * 16) = zero4;
+      }
+      wait_vm<0>();
+      __syncthreads();
+#pragma unroll      // (unrolled on purpose: as a rolled loop the k-step's fragment addresses took 238 VGPRs, 7 more)
+      for (int ks = 0; ks < 4; ++ks) {
+        uint4 fa[FM], fb[FN];
+        load_a(smem, ks, fa); load_b(smem, ks, fb);
+        mma(fa, fb);
+      }
+    }
+  }
   __syncthreads();     // the ring is dead: every wave has read its last fragments
 
   // ---- epilogue: 32-row blocks through a wave-private LDS patch ----
@@ -261,9 +305,16 @@ __global__ __launch_bounds__(512) void gemm_big_kernel(GemmParams p, int tiles_n
         const float4 x0 = *reinterpret_cast<const float4*>(patch + rl * C::EP_LD + cgi * 8);
         const float4 x1 = *reinterpret_cast<const float4*>(patch + rl * C::EP_LD + cgi * 8 + 4);
         v[0] = x0.x; v[1] = x0.y; v[2] = x0.z; v[3] = x0.w; v[4] = x1.x; v[5] = x1.y; v[6] = x1.z; v[7] = x1.w;
-        if constexpr (PART) {
+        if constexpr (EPI == EP_PART) {
           float4* q = reinterpret_cast<float4*>(p.ws + ((int64_t)zsplit * p.M + (mb + rl)) * p.N + nb);
           q[0] = x0; q[1] = x1;
+        } else if constexpr (EPI == EP_GROUP) {
+          float4* q = reinterpret_cast<float4*>(reinterpret_cast<float*>(p.C) + (int64_t)(mb + rl) * p.ldc + nb);
+          if (p.accumulate) {
+            const float4 c0 = q[0], c1 = q[1];
+            v[0] += c0.x; v[1] += c0.y; v[2] += c0.z; v[3] += c0.w; v[4] += c1.x; v[5] += c1.y; v[6] += c1.z; v[7] += c1.w;
+          }
+          q[0] = make_float4(v[0], v[1], v[2], v[3]); q[1] = make_float4(v[4], v[5], v[6], v[7]);
         } else {
           epilogue_store8(p, mb + rl, nb, v);
         }
@@ -276,6 +327,42 @@ __global__ __launch_bounds__(512) void gemm_big_kernel(GemmParams p, int tiles_n
   if constexpr (FM > 2) block(std::integral_constant<int, 2>{});
   if constexpr (FM > 3) block(std::integral_constant<int, 3>{});
   static_assert(FM <= 4, "row blocks");
+}
+
+template <typename C, bool PART = false>
+__global__ __launch_bounds__(512) void gemm_big_kernel(GemmParams p, int tiles_n) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  // XCD-aware tile order: workgroup ids go round-robin to the 8 XCDs; every XCD gets a contiguous band of tiles, n fastest
+  const int total = gridDim.x, lin = blockIdx.x;
+  const int q8 = total >> 3, r8 = total & 7, xcd = lin & 7, slot = lin >> 3;
+  int tile = xcd * q8 + min(xcd, r8) + slot;
+  // (PART: the order above runs over the whole launch, slice-major: the tiles of one k-range are neighbours on an XCD)
+  // k-tiles: `ktiles` full ones, then the tail where the operands allow one (both mn-major) and this workgroup's range ends at K
+  constexpr bool TAIL = !C::AK && !C::BK;
+  const int kfull = p.K / 64;
+  int zsplit = 0, kt0 = 0, ktiles = kfull, tail = TAIL ? walk_tail_pieces(p.K) : 0;
+  if constexpr (PART) {
+    const int tiles = total / p.split_k;
+    zsplit = tile / tiles;
+    tile -= zsplit * tiles;
+    kt0 = zsplit * p.kt_per_split;
+    const int kend = kt0 + p.kt_per_split;      // the host's ranges count the tail as a k-tile: (K + 63) / 64
+    ktiles = min(kfull, kend) - kt0;
+    if (TAIL && kend <= kfull) tail = 0;
+  }
+  const int m0 = (tile / tiles_n) * C::BM, n0 = (tile % tiles_n) * C::BN;
+  gemm_big_body<C, PART ? EP_PART : EP_FUSED>(p, smem, m0, n0, zsplit, kt0, ktiles, tail);
+}
+
+// Grouped form on the (mn, mn) 384 x 192 tile: the tiles of up to GEMM_GROUP_MAX problems numbered consecutively (the tiles of one
+// problem contiguous, n fastest: the tiles that share an A = dy panel are neighbours), the XCD-aware order over the whole launch,
+// every workgroup the whole K of its tile: no split, no workspace, no atomics, the same bits on every run.
+template <typename C>
+__global__ __launch_bounds__(512) void gemm_big_group_kernel(BigGroup g) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const WalkTile w = walk_group_tile(walk_xcd_tile(blockIdx.x, gridDim.x), g.first_tile, g.tiles_n, g.n, C::BM, C::BN);
+  const BigGroupProblem& q = g.q[w.problem];
+  gemm_big_body<C, EP_GROUP>(q, smem, w.m0, w.n0, 0, 0, q.K / 64, walk_tail_pieces(q.K));
 }
 
 template <typename C, bool PART = false>
@@ -368,7 +455,7 @@ int launch_gemm_big(const GemmParams& p, bool b_kmajor, hipStream_t st) {
 // 72 KiB per 9.4 MFLOP: half the bytes.  tiles x split_k one-per-CU workgroups; partials leave as plain fp32 (PART) and
 // peneo_gemm's split-k reduce applies `accumulate`.
 // Taken only when ALL hold (everything else stays on its kernel): fp32 C, no epilogue option beyond accumulate, no a_colsum,
-// M % 384 == 0, N % 192 == 0, K % 64 == 0, 16-byte aligned C / workspace rows, and K >= NN_MIN_K.
+// M % 384 == 0, N % 192 == 0, K % 8 == 0, 16-byte aligned C / workspace rows, and K >= NN_MIN_K.
 //   NN_MIN_K = 65536: the other (mn, mn) callers contract over the tokens of a batch (encoder / patch-embedding / decoder-input
 //   weight gradients: K <= 8192 at every configuration), where the 128 x 128 kernel's M N / 16384 tiles x its own split fill the
 //   chip and a workgroup's range is a few k-tiles; dW1 contracts over pairs (K = 8256 per document of 128 lines, 1 081 344 at the
@@ -390,7 +477,7 @@ static int nn_mode() {
 static bool nn_shape_ok(int M, int N, int K) {
   const int mode = nn_mode();
   if (mode == 0 || M <= 0 || N <= 0 || K <= 0) return false;
-  if (M % BigNN384::BM != 0 || N % BigNN384::BN != 0 || K % 64 != 0) return false;
+  if (M % BigNN384::BM != 0 || N % BigNN384::BN != 0 || K % 8 != 0) return false;
   return mode != 1 || K >= NN_MIN_K;
 }
 
@@ -409,6 +496,60 @@ int launch_gemm_big_nn(const GemmParams& p, hipStream_t st) {
   return p.split_k > 1 ? launch_big<BigNN384, true>(p, st) : launch_big<BigNN384, false>(p, st);
 }
 
+// ---- the grouped form: up to GEMM_GROUP_MAX (mn, mn) weight gradients as ONE launch of whole-K 384 x 192 tiles ----
+// An encoder layer's four weight gradients are 24 + 32 + 32 + 8 = 96 such tiles: 96 one-per-CU workgroups that stage 72 KiB per
+// k-tile, half the bytes of the 432 tiles of 128 x 128.  peneo_gemm_group takes this path only when EVERY problem of the
+// call passes the rule, which is launch_gemm_big_nn's without the K bound and without a split:
+//   bf16 operands, A [K][M], B [K][N], fp32 C, no epilogue option beyond accumulate, M % 384 == 0, N % 192 == 0, K % 8 == 0,
+//   16-byte aligned operands and C rows, 64 rows of A or B below 2 GiB, and the mode allows it.
+static int g_group_nn_mode = -1;   // PENEO_WGRAD_NN384: 0 = off, 1 = on (default, by measurement: DESIGN 32), 2 = on except for the layer the encoder backward issues last
+static std::atomic<uint64_t> g_group_nn_launches{0};
+
+static int group_nn_mode() {
+  if (g_group_nn_mode < 0) {      // read once; a negative value of the variable is 0, as in the setter
+    const char* e = getenv("PENEO_WGRAD_NN384");
+    const int v = e ? atoi(e) : 1;
+    g_group_nn_mode = v < 0 ? 0 : v;
+  }
+  return big_mode() == 0 ? 0 : g_group_nn_mode;
+}
+
+int launch_gemm_big_group(const GemmParams* ps, int n, hipStream_t st) {
+  if (group_nn_mode() == 0 || n < 1 || n > GEMM_GROUP_MAX) return 0;
+  BigGroup g;
+  g.n = n;
+  int Ms[GEMM_GROUP_MAX], Ns[GEMM_GROUP_MAX];
+  for (int i = 0; i < GEMM_GROUP_MAX; ++i) {
+    const GemmParams& p = ps[i < n ? i : n - 1];
+    if (i < n) {
+      Ms[i] = p.M; Ns[i] = p.N;
+      const peneo_gemm_epilogue& e = p.ep;
+      if (p.c_dtype != PENEO_F32 || p.dz_on || p.split_k > 1 || e.bias || e.preact || e.grad_src || e.residual || e.a_colsum ||
+          e.act != PENEO_ACT_NONE || e.drop_p != 0.f || e.alpha != 1.f)
+        return 0;
+      if (p.M <= 0 || p.N <= 0 || p.K < 8 || p.M % BigNN384::BM != 0 || p.N % BigNN384::BN != 0 || p.K % 8 != 0) return 0;
+      if ((reinterpret_cast<uintptr_t>(p.A) | reinterpret_cast<uintptr_t>(p.B) | reinterpret_cast<uintptr_t>(p.C)) & 15) return 0;
+      if (p.lda % 8 != 0 || p.ldb % 8 != 0 || p.ldc % 4 != 0) return 0;
+      // per-lane source offsets are 32-bit: 64 rows of the operand
+      if ((int64_t)64 * p.lda * 2 >= ((int64_t)1 << 31) || (int64_t)64 * p.ldb * 2 >= ((int64_t)1 << 31)) return 0;
+    }
+    BigGroupProblem& q = g.q[i];
+    q.A = p.A; q.B = p.B; q.C = p.C; q.lda = p.lda; q.ldb = p.ldb; q.ldc = p.ldc; q.M = p.M; q.N = p.N; q.K = p.K;
+    q.accumulate = p.ep.accumulate ? 1 : 0;
+  }
+  const int tiles = walk_group_fill(Ms, Ns, n, GEMM_GROUP_MAX, BigNN384::BM, BigNN384::BN, g.first_tile, g.tiles_n);
+  static std::atomic<uint64_t> lds_devices{0};
+  if (!allow_dynamic_lds(reinterpret_cast<const void*>(gemm_big_group_kernel<BigNN384>), BigNN384::LDS_BYTES, lds_devices))
+    return dynamic_lds_error("peneo_gemm_group", BigNN384::LDS_BYTES);
+  hipLaunchKernelGGL((gemm_big_group_kernel<BigNN384>), dim3((unsigned)tiles), dim3(512), BigNN384::LDS_BYTES, st, g);
+  const int rc = check_launch("peneo_gemm_group (384 x 192 tiles)");
+  if (rc != PENEO_OK) return rc;
+  g_group_nn_launches.fetch_add(1, std::memory_order_relaxed);
+  return 1;
+}
+
+int gemm_group_nn384_mode() { return group_nn_mode(); }
+
 }  // namespace peneo
 
 /* tools/ only (not in the header): 0 = off, 1 = choose by the cost model, 256 / 384 / 128 = force that tile shape */
@@ -419,3 +560,7 @@ extern "C" void peneo_gemm_set_nn384_mode(int mode) { peneo::g_nn_mode = mode; }
 extern "C" int peneo_gemm_nn384_mode(void) { return peneo::nn_mode(); }
 extern "C" int peneo_gemm_nn384_shape_ok(int M, int N, int K) { return peneo::nn_shape_ok(M, N, K) ? 1 : 0; }
 extern "C" uint64_t peneo_gemm_nn384_launches(void) { return peneo::g_nn_launches.load(std::memory_order_relaxed); }
+/* grouped weight gradients on the 384 x 192 tile: 0 = off, 1 = on, 2 = on except for the layer peneo_encoder_layer_bwd is told is last */
+extern "C" void peneo_gemm_group_set_nn384_mode(int mode) { peneo::g_group_nn_mode = mode < 0 ? 0 : mode; }
+extern "C" int peneo_gemm_group_nn384_mode(void) { return peneo::group_nn_mode(); }
+extern "C" uint64_t peneo_gemm_group_nn384_launches(void) { return peneo::g_group_nn_launches.load(std::memory_order_relaxed); }

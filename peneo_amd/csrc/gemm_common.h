@@ -24,6 +24,7 @@ struct GemmParams {
   peneo_pair_dz_args dz;
   float* dz_ws;
 };
+constexpr int GEMM_GROUP_MAX = 4;     // problems of one peneo_gemm_group call
 constexpr int GEMM_DZ_SLOTS = 256;   // == DZ_SLOTS of pair_heads.hip (rows of the partial-sum workspace)
 
 
@@ -254,6 +255,9 @@ int launch_gemm_big(const GemmParams& p, bool b_kmajor, hipStream_t st);
 // gemm_big.hip, A = [K, M] and B = [K, N]: 384 x 192 tiles x p.split_k k-ranges (partials in p.ws when p.split_k > 1; the caller
 // reduces them).  Same return convention.
 int launch_gemm_big_nn(const GemmParams& p, hipStream_t st);
+// gemm_big.hip, the grouped form of the same tile: ps[0 .. n) all A = [K, M], B = [K, N], whole K per workgroup.  Same return
+// convention; 0 unless every problem passes the rule there and the mode (PENEO_WGRAD_NN384) is on.
+int launch_gemm_big_group(const GemmParams* ps, int n, hipStream_t st);
 // gemm_sk.hip (persistent stream-k launch): same return convention.  A launch whose ranges cut tiles keeps its flags and slabs in
 // the caller's workspace (ws, ws_bytes): at least gemm_sk_workspace_bytes(M, N, K) bytes, 16-byte aligned.
 int launch_gemm_sk(const GemmParams& p, bool b_kmajor, void* ws, size_t ws_bytes, hipStream_t st);

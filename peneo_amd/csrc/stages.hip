@@ -283,7 +283,10 @@ extern "C" int peneo_encoder_layer_bwd(const peneo_encoder_layer* L, const peneo
     pr[1] = {I, H, R, G->d_zi, I, L->a, H, G->dwi, H, 0, nullptr};
     pr[2] = {H, I, R, d_dense2, H, L->inter, I, G->dwo2, I, 0, nullptr};
     pr[3] = {H, H, R, d_dense1, H, L->att, H, G->dwo, H, 0, nullptr};
-    STAGE_TRY(peneo_gemm_group(PENEO_BF16, 0, 0, PENEO_F32, pr, 4, side));
+    // PENEO_WGRAD_NN384 (gemm_big.hip): the group on 96 one-per-CU tiles of 384 x 192 where the shapes are whole tiles;
+    // under mode 2 the layer the caller marks as the backward's last keeps the short 128 x 128 launch (it ends in the step's tail)
+    const bool nn384 = !(gemm_group_nn384_mode() == 2 && L->wgrad_last);
+    STAGE_TRY(gemm_group_launch(PENEO_BF16, 0, 0, PENEO_F32, pr, 4, side, nn384));
   }
   // d_x = dqkv Wqkv + d_h1
   ep = {};

@@ -40,7 +40,7 @@ class EncoderLayer(C.Structure):
                 [("bias_ld", _i64)] +
                 [(n, _vp) for n in ("key_bias", "drop_words", "x", "qkv", "att", "lse", "h1", "m1", "r1", "a", "zi", "inter", "h2",
                                     "m2", "r2")] +
-                [(n, _i) for n in ("B", "T", "H", "nh", "I", "reserved")] +
+                [(n, _i) for n in ("B", "T", "H", "nh", "I", "wgrad_last")] +
                 [(n, _f) for n in ("eps", "attn_scale", "p_hidden", "p_attn")] + [("seed_o", _u32), ("seed_o2", _u32)])
 
 
@@ -230,6 +230,9 @@ SIGNATURES = {
     "peneo_gemm_nn384_shape_ok": (_i, [_i, _i, _i]),
     "peneo_gemm_big_mode": (_i, []),
     "peneo_gemm_nn384_launches": (C.c_uint64, []),
+    "peneo_gemm_group_set_nn384_mode": (None, [_i]),
+    "peneo_gemm_group_nn384_mode": (_i, []),
+    "peneo_gemm_group_nn384_launches": (C.c_uint64, []),
     "peneo_gemm_set_sk_mode": (None, [_i]),
     "peneo_gemm_sk_set_prof": (None, [_vp]),
     "peneo_gemm_sk_set_max_groups": (None, [_i]),

@@ -400,6 +400,7 @@ def _stage_backward(ctx, d_out):
     seeds = st.seeds
     d_out = d_out.contiguous()
     L, keep = _describe_layer(model, st, idx, params, x, bufs)
+    L.wgrad_last = 1 if idx == 0 else 0      # layer 0 runs backward last: its weight gradients end in the step's tail
     main = torch.cuda.current_stream()
     side = model.side_stream(dev) if model.wgrad_on_side_stream else None
     # small fp32 accumulators of all layers: one zero fill per step (the last layer runs backward first)
